@@ -9,6 +9,13 @@ A "step" is one pass of the CG loop body (reference pykrylov/cg/cg.py:113-158: 1
 3 vector updates) on synthetic data resident in HBM.  Tolerances are set to zero so that exactly
 K passes run inside the timed region.
 
+A plain run does only what the headline needs: it sets up the workload, runs W warm-up and K timed passes and prints the
+line (`value`, `ms_per_step` and the recurrence residual of the timed run).  `--full` adds everything else below: the
+roofline's back-to-back kernel timing, the true-residual check, the parity segment, the second workload, the other
+workloads and solver loops, the CPU baselines, and for N > 1 the comm probes and the all-gather run.  `--dump-outputs DIR`
+writes what the timed run computed (DIR/x.npy: the iterate, a fixed seeded sample of at most 2^21 entries of it;
+DIR/resid_history.npy: the residual history of the warm-up and timed passes; float64; rank 0).
+
 OUTPUT.  Rank 0 prints ONE compact JSON line (<= 4096 bytes, `compact_line`): the contract keys, `config`, `roofline`
 (the SpMV kernel: physical bytes / HIP-event time), `iteration_frac`, `residual`, `parity_vs_n1`, `placement_draws`,
 `cpu_baseline`, the second workload as a block of the same shape (`second_workload`), and every other measured loop as
@@ -35,7 +42,7 @@ in bench_detail.json as `csr_equivalent_GBs` -- a throughput in CSR units, not a
 Multi-GPU: one process per GPU.  torch.distributed is used with the gloo backend ONLY, for the bootstrap
 (RCCL unique id, barriers, max over ranks of the elapsed time): the only RCCL instance in a process is the one
 libmikrylov dlopens for the data path (halo send/recv or all-gather before each product, all-reduce of the dot
-partials).  For N > 1 both exchange modes are measured back to back (`exchange`), `value` is the halo one.
+partials).  For N > 1 with --full both exchange modes are measured back to back (`exchange`), `value` is the halo one.
 """
 import argparse
 import ctypes
@@ -429,6 +436,19 @@ def n1_history(workload):
     return np.array(z[key]) if key in z.files else None
 
 
+X_SAMPLE = 1 << 21             # entries of the iterate --dump-outputs keeps (16 MiB; the history adds 8 B per pass)
+
+
+def dump_outputs(out_dir, x, hist):
+    """What the timed run hands its caller, for comparing two builds output for output: the iterate (a fixed seeded
+    sample of it, in index order, when it is longer than X_SAMPLE) and the residual history, float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    if x.size > X_SAMPLE:
+        x = x[np.sort(np.random.default_rng(0).choice(x.size, X_SAMPLE, replace=False))]
+    np.save(os.path.join(out_dir, "x.npy"), np.asarray(x, dtype=np.float64))
+    np.save(os.path.join(out_dir, "resid_history.npy"), np.asarray(hist, dtype=np.float64))
+
+
 # ======================================================================================
 # workloads
 # ======================================================================================
@@ -757,19 +777,26 @@ def main():
     ap.add_argument("--workload", default="auto")
     ap.add_argument("--exchange", default="both", choices=["both", "halo", "allgather"],
                     help="N > 1: iterate exchange before each product.  both: halo is `value`, all-gather is timed "
-                         "beside it with a fifth of the steps")
+                         "beside it with a fifth of the steps (with --full)")
     ap.add_argument("--event-stride", type=int, default=0,
                     help="additionally bracket the SpMV of every k-th pass with its own HIP event pair "
                          "(intrusive: each pair costs ~3-6 us; 0 = off)")
-    ap.add_argument("--spmv-launches", type=int, default=200,
-                    help="back-to-back launches of the fused SpMV kernel timed by one HIP event pair")
+    ap.add_argument("--spmv-launches", type=int, default=None,
+                    help="back-to-back launches of the fused SpMV kernel timed by one HIP event pair (default: 200 with "
+                         "--full, 0 otherwise)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline (module docstring); off: set-up, warm-up, "
+                         "timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed run's iterate (seeded sample) and residual history to DIR/*.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--one-device", action="store_true",
                     help="test aid: every rank on GPU 0 (RCCL refuses that, which exercises the host-staged fallback)")
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the 60-pass parity segment of the 512^3 workloads")
     ap.add_argument("--parity", action="store_true",
-                    help="N = 1: also run the 60-pass parity segment against tests/golden/dev_hist_512.npz (always on for N > 1)")
+                    help="also run the 60-pass parity segment against tests/golden/dev_hist_512.npz (with --full: on for "
+                         "N > 1 and the 512^3 workloads)")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "host"],
                     help="host: collectives staged through host memory over gloo, all ranks on GPU 0 -- a smoke test "
                          "of the N > 1 path on a single-GPU box, not a measurement")
@@ -781,6 +808,8 @@ def main():
     ap.add_argument("--only-other-configs", action="store_true",
                     help="profiling aid: run only configs[2] and configs[3] (BiCGSTAB random, MINRES shifted) and print them")
     args = ap.parse_args()
+    if args.spmv_launches is None:
+        args.spmv_launches = 200 if args.full else 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_spawn(args.gpus)                                 # does not return
@@ -914,24 +943,30 @@ def main():
             barrier()
         timing = run.timing()
         res = run.finish()
-        # the line proves its own work: ||b - A x_k|| recomputed from the iterate with the plain product
-        # (one exchange + one product + one norm, all ranks), against the residual the recurrence carries (cg.py:131,146,154)
-        px = ctypes.c_void_p()
-        _lib.check(lib.mk_solver_x(run.handle, ctypes.byref(px)))
-        xext = _lib.DeviceArray(op.shape[1])
-        _lib.check(lib.mk_memcpy_d2d(xext.ptr, px.value, 8 * n_local))
-        if td is not None:
-            _lib.check(lib.mk_exchange(op.handle, xext.ptr))
-        axb = _lib.DeviceArray(n_local)
-        _lib.check(lib.mk_spmv(op.handle, xext.ptr, axb.ptr))
-        _lib.check(lib.mk_axpy(n_local, -1.0, rhs.ptr, axb.ptr))
-        sq = ctypes.c_double()
-        _lib.check(lib.mk_dot(n_local, axb.ptr, axb.ptr, ctypes.byref(sq)))
-        sqv = (ctypes.c_double * 1)(sq.value)
-        _lib.check(lib.mk_comm_allreduce_host(sqv, 1))
-        true_resid = float(np.sqrt(sqv[0]))
-        xext.free()
-        axb.free()
+        if args.dump_outputs and workload == name and rank == 0:
+            # (before the back-to-back timing below: it launches the fused pass kernel again, which moves x and p)
+            dump_outputs(args.dump_outputs, run.x(), run.history())
+        true_resid = None
+        if args.full:
+            # the line proves its own work: ||b - A x_k|| recomputed from the iterate with the plain
+            # product (one exchange + one product + one norm, all ranks), against the residual the recurrence carries
+            # (cg.py:131,146,154)
+            px = ctypes.c_void_p()
+            _lib.check(lib.mk_solver_x(run.handle, ctypes.byref(px)))
+            xext = _lib.DeviceArray(op.shape[1])
+            _lib.check(lib.mk_memcpy_d2d(xext.ptr, px.value, 8 * n_local))
+            if td is not None:
+                _lib.check(lib.mk_exchange(op.handle, xext.ptr))
+            axb = _lib.DeviceArray(n_local)
+            _lib.check(lib.mk_spmv(op.handle, xext.ptr, axb.ptr))
+            _lib.check(lib.mk_axpy(n_local, -1.0, rhs.ptr, axb.ptr))
+            sq = ctypes.c_double()
+            _lib.check(lib.mk_dot(n_local, axb.ptr, axb.ptr, ctypes.byref(sq)))
+            sqv = (ctypes.c_double * 1)(sq.value)
+            _lib.check(lib.mk_comm_allreduce_host(sqv, 1))
+            true_resid = float(np.sqrt(sqv[0]))
+            xext.free()
+            axb.free()
         comm = None
         if td is not None:
             last = ctypes.c_double()
@@ -968,19 +1003,21 @@ def main():
         assert done == steps and done_w == warmup, (done, steps, done_w, warmup)
         assert np.isfinite(res.residNorm), "CG diverged"
         hist = run.history()
-        rel_gap = abs(true_resid - float(hist[-1])) / float(hist[0])
         info = dict(op_shape=op.shape, nnz=op.nnz, n_local=n_local, n_global=n_global, meta=meta, elapsed=elapsed,
                     timing=timing, resid_first=float(hist[0]), resid_last=float(hist[-1]), comm=comm,
                     fmt=format_info(lib, op), steps=steps, launches=nl, placement=dict(run.placement), parity=parity_info,
                     fused=bool(fz.value),
-                    residual={"first": float(hist[0]), "last": float(hist[-1]), "recurrence": float(hist[-1]), "true": true_resid,
-                              "rel_gap": rel_gap, "passes": int(res.nMatvec),
-                              "note": "true = ||b - A x_k|| recomputed from the iterate after the timed region with the "
-                                      "plain product; rel_gap = |true - recurrence| / ||r_0||, the line fails above 1e-10"})
-        info["residual"]["ok"] = bool(rel_gap <= 1e-10)
-        if not (rel_gap <= 1e-10) and workload == name:       # (the headline fails the line; extras carry ok = false)
-            raise SystemExit("bench.py: %s: recurrence residual %.6e but true residual %.6e (gap / r0 = %.2e > 1e-10): "
-                             "the timed kernels did not do CG's work" % (workload, hist[-1], true_resid, rel_gap))
+                    residual={"first": float(hist[0]), "last": float(hist[-1]), "recurrence": float(hist[-1]),
+                              "passes": int(res.nMatvec)})
+        if true_resid is not None:
+            rel_gap = abs(true_resid - float(hist[-1])) / float(hist[0])
+            info["residual"].update({"true": true_resid, "rel_gap": rel_gap, "ok": bool(rel_gap <= 1e-10),
+                                     "note": "true = ||b - A x_k|| recomputed from the iterate after the timed region with "
+                                             "the plain product; rel_gap = |true - recurrence| / ||r_0||, the line fails "
+                                             "above 1e-10"})
+            if not (rel_gap <= 1e-10) and workload == name:   # (the headline fails the line; extras carry ok = false)
+                raise SystemExit("bench.py: %s: recurrence residual %.6e but true residual %.6e (gap / r0 = %.2e > 1e-10): "
+                                 "the timed kernels did not do CG's work" % (workload, hist[-1], true_resid, rel_gap))
         run.close()
         op.free()
         return info
@@ -1063,9 +1100,9 @@ def main():
 
     def cg_workload(wname, steps, warmup, stride=0, headline=False):
         """One CG workload measured end to end: the detail block both the compact line and bench_detail.json are cut from."""
-        info = run_cg(wname, steps, warmup, stride, exchange=first_mode, comm_probe=multi and headline,
-                      parity=(multi or args.parity or (wname in ("poisson3d-512-varcoef", "poisson3d-512")
-                                                        and not args.no_parity)))
+        info = run_cg(wname, steps, warmup, stride, exchange=first_mode, comm_probe=multi and headline and args.full,
+                      parity=(args.parity or (args.full and (multi or (wname in ("poisson3d-512-varcoef", "poisson3d-512")
+                                                                       and not args.no_parity)))))
         w_its, w_nnz, w_roof, w_it = roofline_of(info, wname)
         blk = {"workload": wname, "value": w_its, "unit": "iterations/s", "steps": steps, "warmup": warmup,
                "ms_per_step": 1e3 * info["elapsed"] / steps, "rows": info["n_global"], "nnz": w_nnz,
@@ -1106,7 +1143,7 @@ def main():
         detail["per_rank_budget"] = budget
         ex = {first_mode: {"value": head["value"], "ms_per_step": head["ms_per_step"], "steps": args.steps,
                            "comm": head["comm"]}}
-        if args.exchange == "both":
+        if args.exchange == "both" and args.full:
             s2 = max(10, args.steps // 5)
             i2 = run_cg(name, s2, max(5, args.warmup // 5), 0, exchange="allgather", comm_probe=True)
             ex["allgather"] = {"value": s2 / i2["elapsed"], "ms_per_step": 1e3 * i2["elapsed"] / s2, "steps": s2,
@@ -1117,15 +1154,16 @@ def main():
         head["roofline"]["note_multi"] = ("N > 1: the SpMV kernel is not timed alone (each launch is preceded by an "
                                           "exchange); see iteration_roofline and exchange.*.comm")
     detail["build_sha"] = _lib.build_info(lib)
-    if not multi and name == "poisson3d-512" and not args.no_extra:
+    extra = args.full and not multi and not args.no_extra
+    if extra and name == "poisson3d-512":
         detail["csr_plain"] = csr_plain_512(lib)
     second = None
-    if not multi and name == "poisson3d-512" and not args.no_extra:
+    if extra and name == "poisson3d-512":
         # the same grid with a VARIABLE coefficient field: no constant-coefficient compression applies, the product streams
         # 8 B per nonzero -- the CSR-class product north_star names, measured beside the literal configs[4] matrix
         second = "poisson3d-512-varcoef"
         detail["workloads"][second] = cg_workload(second, args.steps, args.warmup)
-    if rank == 0 and not multi and not args.no_cpu and not os.environ.get("BENCH_CHILD"):
+    if args.full and rank == 0 and not multi and not args.no_cpu and not os.environ.get("BENCH_CHILD"):
         small = cpu_baseline(name, seconds_budget=8.0 if full_512 else 20.0)
         head["cpu_baseline"] = small
         if full_512:
@@ -1146,7 +1184,7 @@ def main():
                     blk.setdefault("cpu_baseline", small if wname == name else cpu_baseline(wname, seconds_budget=8.0))
                     blk["cpu_baseline"]["full_size_attempt"] = full if not isinstance(full, dict) or "error" in full \
                         or "skipped" in full else got
-    if not multi and full_512 and not args.no_extra:
+    if extra and full_512:
         # the other BASELINE configs and every other solver loop on one GPU, same measurement (bench_detail.json; the
         # compact line carries iterations/s and the physical fraction of each)
         others = [("poisson2d-1000", 2000, 200), ("stencil27-256", 400, 40), ("stencil27-256-varcoef", 200, 20)]

@@ -67,7 +67,7 @@ def test_bench_two_rank_path_smoke(launcher):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3", "--transport", "host",
-            "--workload", "poisson3d-64", "--spmv-launches", "3"]
+            "--workload", "poisson3d-64", "--spmv-launches", "3", "--full"]
     nranks = 2
     if launcher.startswith("self-varcoef"):                 # the default line's operator family, partitioned
         args[args.index("poisson3d-64")] = "poisson3d-64-varcoef"

@@ -7,9 +7,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
-REF_EXAMPLES = "/root/reference/examples"
+from conftest import GOLDEN, ROOT
 
 
 def same(a, b):
@@ -154,12 +152,11 @@ def test_coo_to_csr_duplicates_and_order():
 
 
 # ------------------------------------------------------------------ MatrixMarket
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLES), reason="reference examples not on this box")
 @pytest.mark.parametrize("name,fix", [("1138bus.mtx", "cg_1138bus.npz"), ("jpwh_991.mtx", "nonsym_jpwh991.npz")])
 def test_read_mtx_reference_examples(golden, name, fix):
     from pykrylov_amd.mmio import read_mtx
     d = golden(fix)
-    indptr, indices, data, shape, symmetric = read_mtx(os.path.join(REF_EXAMPLES, name))
+    indptr, indices, data, shape, symmetric = read_mtx(os.path.join(GOLDEN, name))
     assert same(indptr, d["A_indptr"]) and same(indices, d["A_indices"]) and same(data, d["A_data"])
     assert shape == tuple(d["A_shape"]) and symmetric == (name == "1138bus.mtx")
 

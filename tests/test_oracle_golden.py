@@ -9,9 +9,8 @@ import os
 import numpy as np
 import pytest
 
+from conftest import GOLDEN
 from oracle import csr_ref, krylov_ref as kr
-
-REF_EXAMPLES = "/root/reference/examples"
 
 
 def csr_from(d, prefix):
@@ -56,11 +55,10 @@ def test_random_builder_bit_exact(golden):
         assert same(getattr(A, k), d["A_" + k])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLES), reason="reference examples not present on this box")
 @pytest.mark.parametrize("name,fix", [("1138bus.mtx", "cg_1138bus.npz"), ("jpwh_991.mtx", "nonsym_jpwh991.npz")])
 def test_matrix_market_reader_bit_exact(golden, name, fix):
     d = golden(fix)
-    A = csr_ref.read_matrix_market(os.path.join(REF_EXAMPLES, name))
+    A = csr_ref.read_matrix_market(os.path.join(GOLDEN, name))
     for k in ("indptr", "indices", "data"):
         assert same(getattr(A, k), d["A_" + k])
 

@@ -14,7 +14,7 @@ for spec in "$@"; do
   i=0
   for set in "${SETS[@]}"; do
     i=$((i+1))
-    env "${EV[@]}" rocprofv3 --pmc $set -f csv -d $OUT/${label}_p$i -o b -- python $R/bench.py --workload $wl --steps 20 --warmup 5 --no-cpu --no-extra --spmv-launches 10 > /dev/null 2> $OUT/${label}_p$i.err
+    env "${EV[@]}" rocprofv3 --pmc $set -f csv -d $OUT/${label}_p$i -o b -- python $R/bench.py --full --workload $wl --steps 20 --warmup 5 --no-cpu --no-extra --spmv-launches 10 > /dev/null 2> $OUT/${label}_p$i.err
   done
 done
 cd $R

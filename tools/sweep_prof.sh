@@ -6,7 +6,7 @@ cd /tmp; export TMPDIR=/tmp
 for cfg in "$@"; do
   gs=${cfg%%:*}; gt=${cfg##*:}
   rm -rf /tmp/sw_prof
-  MK_GRID_SPMV=$gs MK_GRID_STREAM=$gt rocprofv3 --kernel-trace --stats -f csv -d /tmp/sw_prof -o s -- python $R/bench.py --workload $WL $BARGS --no-cpu --no-extra >/tmp/sw.json 2>/dev/null
+  MK_GRID_SPMV=$gs MK_GRID_STREAM=$gt rocprofv3 --kernel-trace --stats -f csv -d /tmp/sw_prof -o s -- python $R/bench.py --full --workload $WL $BARGS --no-cpu --no-extra >/tmp/sw.json 2>/dev/null
   python - "$gs" "$gt" <<'PY'
 import csv,glob,sys,json
 rows=list(csv.DictReader(open(glob.glob('/tmp/sw_prof/**/*kernel_stats.csv',recursive=True)[0])))

@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/trace_series; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -f csv -d $OUT/t -o b -- python $R/bench.py --steps 3000 --warmup 50 --no-cpu --no-extra --spmv-launches 0 > $OUT/bench.json 2> $OUT/err.txt
+rocprofv3 --kernel-trace -f csv -d $OUT/t -o b -- python $R/bench.py --full --steps 3000 --warmup 50 --no-cpu --no-extra --spmv-launches 0 > $OUT/bench.json 2> $OUT/err.txt
 cd $R
 python - "$OUT" <<'PY'
 import csv, glob, sys, collections

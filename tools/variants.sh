@@ -7,6 +7,7 @@ L=$PWD/pykrylov_amd
 run() {   # name, env..., -- args
   name=$1; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
+  set -- --full "$@"      # (the summary below reads the roofline's back-to-back kernel time)
   env "${envs[@]}" timeout 300 python bench.py --no-cpu --no-extra --steps 300 --warmup 30 "$@" > gpurun_out/var/$name.json 2> gpurun_out/var/$name.err
 }
 for wl in poisson3d-512-varcoef poisson3d-512; do
