@@ -445,6 +445,41 @@ MK_API int mk_solver_set_precon_callback(mk_solver *s, mk_precon_fn fn, void *us
  * of the solver's (local) size, without an exchange plan (on several GPUs: a rank-local preconditioner).  NULL
  * removes it.  Call before mk_solver_setup. */
 MK_API int mk_solver_set_precon_csr(mk_solver *s, const mk_csr *M);
+/* Incomplete factorizations of a device matrix A as preconditioners M ~ A (`precon * r` = M^-1 r, generic/generic.py:76),
+ * on the pattern of A in CSR column order (stored zeros included; every row must store its diagonal: MK_ERR_ARG otherwise):
+ *   mk_ilu0_create: ILU(0), Saad Alg. 10.4 (IKJ form): L unit lower triangular, U upper triangular.  A zero pivot U_ii = 0
+ *                   fails with MK_ERR_STATE naming the smallest such row.
+ *   mk_ic0_create:  IC(0) of a symmetric matrix (pattern checked; the values of the lower triangle are used): M = L L^T.
+ *                   A pivot that is not positive fails with MK_ERR_STATE naming the row.
+ * The factor is computed on the device, one launch per level of the forward dependency graph (a host analysis of the
+ * pattern groups the rows).  It borrows A's pattern (A may be destroyed meanwhile: it lives on until the factor goes) and
+ * owns its values (8 bytes per nonzero) and the row lists of both sweeps.  MK_ERR_UNSUPPORTED for operators that hold no
+ * arrays of their own (sums, products, reduced, block, composed, matrix-free: form the matrix first), for operators with an
+ * exchange plan, and for nnz >= 2^31.  MK_ERR_ARG for a non-square matrix. */
+typedef struct mk_ilu mk_ilu;
+MK_API int mk_ilu0_create(const mk_csr *A, mk_ilu **out);
+MK_API int mk_ic0_create(const mk_csr *A, mk_ilu **out);
+/* Destroying a factor that solvers still hold (mk_solver_set_precon_ilu) is deferred until the last of them goes. */
+MK_API int mk_ilu_destroy(mk_ilu *F);
+/* out = M^-1 in on device vectors (in == out allowed): forward sweep t_i = r_i - sum_{j<i} L_ij t_j (IC(0): then / l_ii),
+ * backward sweep y_i = (t_i - sum_{j>i} U_ij y_j) / U_ii, each row summed left to right in column order.  Rows are
+ * solved level by level: one launch per level, or one workgroup for a run of consecutive levels of at most
+ * MK_ILU_FUSE_ROWS rows each (environment, read when the factor is created; default 256, 0 = one launch per level). */
+MK_API int mk_ilu_apply(const mk_ilu *F, const double *in_dev, double *out_dev);
+/* info[k] for k < min(cap, MK_ILU_INFO_LEN): 0 kind (0 ILU(0), 1 IC(0)), 1 rows, 2 nonzeros, 3 / 4 levels of the forward /
+ * backward sweep, 5 / 6 launches of the forward / backward sweep, 7 rows of the widest level, 8 device bytes held,
+ * 9 fusion threshold in rows, 10 host analysis time (us), 11 factorization time (us). */
+#define MK_ILU_INFO_LEN 12
+MK_API int mk_ilu_info(const mk_ilu *F, int64_t *info, int32_t cap);
+/* The factor to the host: values on A's pattern (nnz doubles; ILU(0): L left of the diagonal, U from it on; IC(0): L
+ * left of and on the diagonal, L^T right of it) and the position of every row's diagonal entry (nrows).  Either may be
+ * NULL. */
+MK_API int mk_ilu_download(const mk_ilu *F, double *values_host, int32_t *diag_host);
+/* ... and as the preconditioner of the six square solvers: applied on the device at the sites of the callback (no host
+ * round trip), every launch obeying the loop's halt words (nothing changes once the loop has ended).  The solver holds a
+ * reference until it is destroyed or the preconditioner is replaced.  Replaces a diagonal, matrix or callback
+ * preconditioner; those setters replace it in turn.  NULL removes it.  Single GPU.  Call before mk_solver_setup. */
+MK_API int mk_solver_set_precon_ilu(mk_solver *s, const mk_ilu *F);
 /* The least-squares kinds take two preconditioners, applied by the reference as `u = M(Mu)` in the m-space and
  * `v = N(Nv)` in the n-space of the Golub-Kahan process (lls/lsqr.py:189-190,201-202,253-254,265-266 and the same
  * lines of lsmr.py, craig.py, craigmr.py): device arrays with the diagonals of M (nrows(A) entries) and N

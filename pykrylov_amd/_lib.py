@@ -33,6 +33,8 @@ class MkRowOp(ctypes.Structure):
                 ("diag", ctypes.c_void_p)]
 
 
+MK_ILU_INFO_LEN = 12      # entries of mk_ilu_info (include/mikrylov.h)
+
 MK_ROW_SCALE, MK_ROW_ADD, MK_ROW_SUB, MK_ROW_RSUB, MK_ROWPROG_MAX = 1, 2, 3, 4, 4
 
 
@@ -128,6 +130,13 @@ PROTOTYPES = {
     "mk_solver_set_precon_diag": (ctypes.c_int, [c_vp, c_vp]),
     "mk_solver_set_precon_callback": (ctypes.c_int, [c_vp, PRECON_FN, c_vp]),
     "mk_solver_set_precon_csr": (ctypes.c_int, [c_vp, c_vp]),
+    "mk_ilu0_create": (ctypes.c_int, [c_vp, P(c_vp)]),
+    "mk_ic0_create": (ctypes.c_int, [c_vp, P(c_vp)]),
+    "mk_ilu_destroy": (ctypes.c_int, [c_vp]),
+    "mk_ilu_apply": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mk_ilu_info": (ctypes.c_int, [c_vp, P(c_i64), c_i32]),
+    "mk_ilu_download": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mk_solver_set_precon_ilu": (ctypes.c_int, [c_vp, c_vp]),
     "mk_solver_set_lls_precon_callback": (ctypes.c_int, [c_vp, PRECON_FN, c_vp, PRECON_FN, c_vp]),
     "mk_solver_set_lls_precon": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mk_solver_setup": (ctypes.c_int, [c_vp, c_vp, c_vp]),

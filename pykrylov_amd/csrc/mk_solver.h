@@ -30,6 +30,13 @@ int mk_comm_allgather(const double *mine_dev, double *full_dev, int64_t count_pe
 int mk_exchange_begin(const mk_csr *A, double *x_ext);     // may leave the messages in flight on a second stream
 int mk_exchange_wait(const mk_csr *A, hipStream_t stream); // ... until here
 
+// Incomplete factorizations (mk_ilu.hip): out = M^-1 in on `stream` (in == out allowed); every launch takes the halt word
+// flags[(*q)++ & 1] (q null: never halted).  A solver holds a factor with mk_ilu_hold and lets go with mk_ilu_release.
+int mk_ilu_enqueue(const mk_ilu *F, const double *in, double *out, hipStream_t stream, int *flags, int64_t *q);
+int64_t mk_ilu_rows(const mk_ilu *F);
+void mk_ilu_hold(const mk_ilu *F);
+void mk_ilu_release(const mk_ilu *F);
+
 struct mk_solver {
     const mk_csr *A = nullptr;
     const mk_csr *At = nullptr;     // transposed matrix (least-squares solvers only)
@@ -44,6 +51,9 @@ struct mk_solver {
     // diagonal blocks of block-Jacobi, as a device matrix or composite): the same sites, the product stays in HBM
     const mk_csr *precon_op = nullptr;
     double *d_ptmp = nullptr;       // product target when a site preconditions a vector in place
+    // ... or through an incomplete factorization (mk_solver_set_precon_ilu: ILU(0) / IC(0)): two level-scheduled triangular
+    // sweeps on the device at the same sites, in place
+    const mk_ilu *precon_ilu = nullptr;
     int *d_nohalt = nullptr;        // two zero words: the halt input of a product that must run after the loop has ended
     int host_precon(const double *in_dev, double *out_dev, bool force = false);   // out = precon * in ; unless `force`, a no-op once the loop has halted
     mk_params prm{};

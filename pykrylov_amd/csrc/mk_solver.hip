@@ -38,6 +38,12 @@ static int mk_precon_on_device(void *, const double *, double *) { return 1; }
 
 int mk_solver::host_precon(const double *in_dev, double *out_dev, bool force) {
     if (!precon_fn) return MK_OK;
+    if (precon_ilu) {
+        // out = M^-1 in by the factor's sweeps; each launch obeys the halt words like the product below
+        const int rc = force ? mk_ilu_enqueue(precon_ilu, in_dev, out_dev, stream, nullptr, nullptr)
+                             : mk_ilu_enqueue(precon_ilu, in_dev, out_dev, stream, d_halt, &q);
+        return rc != MK_OK ? rc : mk_ctx().pending_rc;
+    }
     if (precon_op) {
         // out = precon_op * in on the device.  Like every kernel of the loop the product obeys the halt words: once the
         // loop condition has failed it is a no-op, exactly when the reference applies nothing more -- unless `force`.
@@ -71,6 +77,7 @@ int mk_solver::host_precon(const double *in_dev, double *out_dev, bool force) {
 mk_solver::~mk_solver() {
     if (mk_ctx().ready) hipStreamSynchronize(mk_ctx().stream);
     if (precon_op) mk_release_operand(precon_op);
+    if (precon_ilu) mk_ilu_release(precon_ilu);
     if (At) mk_release_operand(At);
     if (A && counted_user) mk_csr_count_users(A, -1);
     if (A) mk_release_operand(A);
@@ -333,6 +340,11 @@ extern "C" int mk_solver_set_precon_diag(mk_solver *s, const double *diag) {
     MK_ARG(MK_ALIGNED16(diag));
     if (diag && !s->takes_precon())
         return mk_fail(MK_ERR_UNSUPPORTED, "this solver kind has no device preconditioner hook");
+    if (s->precon_ilu) {                                     // a diagonal replaces an incomplete factorization
+        mk_ilu_release(s->precon_ilu);
+        s->precon_ilu = nullptr;
+        s->precon_fn = nullptr;
+    }
     s->d_prec = diag;
     return MK_OK;
 }
@@ -341,10 +353,16 @@ __global__ __launch_bounds__(MK_BLOCK) void mk_fill_kernel(double *v, int64_t n,
     for (int64_t i = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MK_BLOCK) v[i] = a;
 }
 
+static void mk_drop_precon_ilu(mk_solver *s) {
+    if (s->precon_ilu) mk_ilu_release(s->precon_ilu);
+    s->precon_ilu = nullptr;
+}
+
 extern "C" int mk_solver_set_precon_callback(mk_solver *s, mk_precon_fn fn, void *user) {
     MK_ARG(s);
     if (s->precon_op) mk_release_operand(s->precon_op);
     s->precon_op = nullptr;
+    mk_drop_precon_ilu(s);
     if (!fn) {
         s->precon_fn = nullptr;
         s->d_prec = nullptr;
@@ -372,6 +390,7 @@ extern "C" int mk_solver_set_precon_callback(mk_solver *s, mk_precon_fn fn, void
 extern "C" int mk_solver_set_precon_csr(mk_solver *s, const mk_csr *M) {
     MK_ARG(s);
     if (!M) {
+        mk_drop_precon_ilu(s);
         if (s->precon_op) mk_release_operand(s->precon_op);
         s->precon_op = nullptr;
         s->precon_fn = nullptr;
@@ -395,8 +414,41 @@ extern "C" int mk_solver_set_precon_csr(mk_solver *s, const mk_csr *M) {
         MK_HIP(hipMemsetAsync(s->d_nohalt, 0, 2 * sizeof(int), s->stream));
     }
     M->dependents += 1;
+    mk_drop_precon_ilu(s);
     if (s->precon_op) mk_release_operand(s->precon_op);
     s->precon_op = M;
+    s->precon_fn = mk_precon_on_device;                      // (marks "general preconditioner" at the call sites)
+    s->precon_user = nullptr;
+    s->d_prec = s->d_ones;
+    return MK_OK;
+}
+
+extern "C" int mk_solver_set_precon_ilu(mk_solver *s, const mk_ilu *F) {
+    MK_ARG(s);
+    if (!F) {
+        mk_drop_precon_ilu(s);
+        s->precon_fn = nullptr;
+        s->d_prec = nullptr;
+        return MK_OK;
+    }
+    if (!s->takes_precon()) return mk_fail(MK_ERR_UNSUPPORTED, "this solver kind has no preconditioner hook");
+    if (s->A->ex.mode >= 0)
+        return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_set_precon_ilu: incomplete factorizations are single-GPU (the solver's "
+                       "operator carries an exchange plan)");
+    if (mk_ilu_rows(F) != s->n)
+        return mk_fail(MK_ERR_ARG, "mk_solver_set_precon_ilu: the factor has %lld rows, the solver %lld",
+                       (long long)mk_ilu_rows(F), (long long)s->n);
+    const size_t len = (size_t)(s->n > 0 ? s->n : 1);
+    if (!s->d_ones) {
+        MK_HIP(hipMalloc((void **)&s->d_ones, sizeof(double) * len + 16));
+        hipLaunchKernelGGL(mk_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, s->stream, s->d_ones, (int64_t)len, 1.0);
+        MK_HIP(hipGetLastError());
+    }
+    mk_ilu_hold(F);                                          // take the new reference first, then drop the old ones
+    mk_drop_precon_ilu(s);
+    if (s->precon_op) mk_release_operand(s->precon_op);
+    s->precon_op = nullptr;
+    s->precon_ilu = F;
     s->precon_fn = mk_precon_on_device;                      // (marks "general preconditioner" at the call sites)
     s->precon_user = nullptr;
     s->d_prec = s->d_ones;

@@ -94,6 +94,16 @@ class KrylovMethod(object):
         if diag is not None and not callable(diag):
             n = self.op.shape[0]
             return as_f64_vector(diag, getattr(self.op, 'local_size', None) or n, 'precon.diag')
+        # * an incomplete factorization (`tools.ilu0` / `tools.ic0`) is applied ON the device by its triangular sweeps
+        from .tools import IluPreconditioner
+        if isinstance(precon, IluPreconditioner):
+            if getattr(self.op, 'local_size', None) is not None:
+                raise NotImplementedError('%s: incomplete factorizations are single-GPU; the operator is row-partitioned'
+                                          % self.__class__.__name__)
+            if precon.shape != (self.op.shape[0], self.op.shape[0]):
+                raise ValueError('%s: precon has shape %s, expected %s'
+                                 % (self.__class__.__name__, precon.shape, (self.op.shape[0], self.op.shape[0])))
+            return precon
         # * a device matrix (CsrOperator -- e.g. the inverted diagonal blocks of `tools.block_jacobi`) or a block
         #   operator of device matrices is applied ON the device, as a product at the same sites
         from .linop import CsrOperator
@@ -192,6 +202,16 @@ class DeviceRun(object):
                 raise
         self.host_precon = None
         self.device_precon = None
+        self.ilu_precon = None
+        from .tools import IluPreconditioner
+        if isinstance(precon_diag, IluPreconditioner):
+            self.ilu_precon, precon_diag = precon_diag, None
+            try:
+                _lib.check(self.lib.mk_solver_set_precon_ilu(self.handle, self.ilu_precon._live()))
+            except Exception:
+                self.lib.mk_solver_destroy(self.handle)
+                self.handle = ctypes.c_void_p()
+                raise
         if isinstance(precon_diag, DevicePrecon):
             self.device_precon, precon_diag = precon_diag, None
             try:
@@ -296,6 +316,8 @@ class DeviceRun(object):
             _lib.check(self.lib.mk_solver_set_transpose(handle, self.transpose.handle))
         if self.device_precon is not None:
             _lib.check(self.lib.mk_solver_set_precon_csr(handle, self.device_precon.dev.handle))
+        if self.ilu_precon is not None:
+            _lib.check(self.lib.mk_solver_set_precon_ilu(handle, self.ilu_precon._live()))
         if self.d_prec is not None:
             _lib.check(self.lib.mk_solver_set_precon_diag(handle, self.d_prec.ptr))
 

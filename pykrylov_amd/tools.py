@@ -4,6 +4,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .linop import LinearOperator
 
 
 def machine_epsilon():
@@ -135,3 +136,115 @@ def block_jacobi(op, block_size):
     ip = np.zeros(n + 1, dtype=np.int64)
     ip[1:] = np.cumsum(np.bincount(r, minlength=n))
     return CsrOperator(ip, c, v, (n, n), symmetric=bool(getattr(op, 'symmetric', False)))
+
+
+def _ilu_operator(op, what, symmetric=False):
+    """Shape / kind checks shared by `ilu0` and `ic0`, made before the device is touched."""
+    shape = getattr(op, 'shape', None)
+    if shape is None or len(shape) != 2:
+        raise TypeError('%s needs an operator with a `.shape`; got %r' % (what, type(op).__name__))
+    if shape[0] != shape[1]:
+        raise ValueError('%s needs a square operator, got shape %s' % (what, (shape,)))
+    if symmetric and not getattr(op, 'symmetric', False):
+        raise ValueError('%s needs a symmetric operator (declared with symmetric=True)' % what)
+    if getattr(op, 'local_size', None) is not None:
+        raise NotImplementedError('%s: the operator is row-partitioned; the incomplete factorizations are single-GPU '
+                                  '(rank-local factors are not available)' % what)
+    from .linop import CsrOperator
+    if not isinstance(op, CsrOperator):
+        raise TypeError('%s: %r holds no CSR arrays on the device; form its matrix (e.g. `to_csr_arrays()` of a device '
+                        'operator) and wrap it in a CsrOperator to factor it' % (what, type(op).__name__))
+    return op
+
+
+def ilu0(op):
+    """ILU(0) of a square device matrix (a :class:`CsrOperator`) as a DEVICE preconditioner: the factor is computed on the
+    GPU on the pattern of `op` (every row must store its diagonal), and ``precon * r`` -- inside a solver's loop or on a
+    NumPy vector -- is the pair of level-scheduled triangular solves ``U^-1 L^-1 r`` (mk_ilu_apply).  Passed as
+    ``precon=`` to CG / BiCGSTAB / CGS / TFQMR / MINRES / SYMMLQ it is applied at the reference's preconditioner sites
+    without a host round trip.  Raises MkError on a zero pivot (naming the row)."""
+    _ilu_operator(op, 'ilu0')
+    return IluPreconditioner(op, 0)
+
+
+def ic0(op):
+    """IC(0) (incomplete Cholesky, no fill) of a symmetric device matrix: ``M = L L^T`` on the lower pattern of `op`, as a
+    symmetric device preconditioner like :func:`ilu0` (MINRES' symmetry check of the preconditioner passes).  Raises
+    ValueError for an operator not declared symmetric, MkError for a pattern that is not symmetric or a pivot that is not
+    positive (naming the row)."""
+    _ilu_operator(op, 'ic0', symmetric=True)
+    return IluPreconditioner(op, 1)
+
+
+class IluPreconditioner(LinearOperator):
+    """M^-1 of an ILU(0) / IC(0) factor resident in HBM (`ilu0`, `ic0`).  ``self * v`` applies it to a NumPy vector;
+    solvers given it as ``precon=`` apply it on the device (mk_solver_set_precon_ilu).  Attributes: `kind`
+    ('ilu0' / 'ic0'), `levels` and `launches` (forward, backward sweep), `info` (mk_ilu_info as a dict).
+    `free()` releases this object's reference; a solver that still applies the factor keeps it alive."""
+
+    def __init__(self, op, kind):
+        lib = _lib.init()
+        h = ctypes.c_void_p()
+        fn = lib.mk_ic0_create if kind else lib.mk_ilu0_create
+        _lib.check(fn(op.handle, ctypes.byref(h)))
+        self._lib = lib
+        self._handle = h.value
+        self._n = int(op.shape[0])
+        self._nnz = int(op.nnz)
+        self._op = op                      # (its pattern: factor_arrays() pairs it with the values)
+        self.kind = 'ic0' if kind else 'ilu0'
+        self._buf = None
+        LinearOperator.__init__(self, self._n, self._n, matvec=self._apply, symmetric=bool(kind), dtype=np.float64)
+
+    handle = property(lambda self: self._handle, doc="Opaque ``mk_ilu*`` for libmikrylov.")
+
+    @property
+    def info(self):
+        names = ('kind', 'rows', 'nnz', 'levels_forward', 'levels_backward', 'launches_forward', 'launches_backward',
+                 'widest_level', 'bytes', 'fuse_rows', 'analysis_us', 'factor_us')
+        v = (ctypes.c_int64 * _lib.MK_ILU_INFO_LEN)()
+        _lib.check(self._lib.mk_ilu_info(self._live(), v, _lib.MK_ILU_INFO_LEN))
+        return dict(zip(names, (int(x) for x in v)))
+
+    levels = property(lambda self: (self.info['levels_forward'], self.info['levels_backward']))
+    launches = property(lambda self: (self.info['launches_forward'], self.info['launches_backward']))
+
+    def _live(self):
+        if not self._handle:
+            raise ValueError('the factor has been freed')
+        return self._handle
+
+    def _apply(self, r):
+        h = self._live()
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if self._buf is None:
+            self._buf = _lib.DeviceArray(self._n, zero=False)
+        self._buf.upload(r)
+        _lib.check(self._lib.mk_ilu_apply(h, self._buf.ptr, self._buf.ptr))
+        return self._buf.to_numpy()
+
+    def factor_arrays(self):
+        """``(indptr, indices, values, diag)``: the factor on the pattern of the operator (values as described in
+        include/mikrylov.h, mk_ilu_download) and the position of each row's diagonal entry."""
+        h = self._live()
+        indptr, indices, _ = self._op.to_csr_arrays()
+        vals = np.empty(self._nnz, dtype=np.float64)
+        diag = np.empty(self._n, dtype=np.int32)
+        _lib.check(self._lib.mk_ilu_download(h, vals.ctypes.data, diag.ctypes.data))
+        return indptr, indices, vals, diag
+
+    def free(self):
+        if getattr(self, '_buf', None) is not None:
+            self._buf.free()
+            self._buf = None
+        if getattr(self, '_handle', None):
+            try:
+                self._lib.mk_ilu_destroy(self._handle)
+            except Exception:
+                pass
+            self._handle = None
+        self._op = None
+
+    def __del__(self):
+        self.free()
+
