@@ -509,6 +509,13 @@ MK_API int mk_solver_history(const mk_solver *s, double *hist_host, int64_t cap)
  * mk_solver_x / mk_solver_vector always hand out the up-to-date iterate (formed into scratch vectors between passes).
  * Environment MK_CG_FUSE=0 turns it off.  Valid after mk_solver_setup. */
 MK_API int mk_solver_fused(const mk_solver *s, int32_t *fused);
+/* Fused CG passes with a DEFERRED x update (environment MK_CG_XDEFER = m, 1 ... 32; default 8 where a vector is larger than
+ * 256 MiB, else 1): x is an accumulator that the loop never reads, so the product kernel leaves it alone (33 bytes per row
+ * besides the matrix data: p, r in; p, A p out), the directions stay in a ring of m + 1 buffers and one sweep applies m of
+ * them to x -- each `x += alpha p` rounded on its own, in order: every bit unchanged.  mk_solver_iterate applies whatever its
+ * passes left before it returns, so this count -- completed passes whose direction has not reached x yet -- is 0 after every
+ * call (with m = 1 it is 1 between passes: that update rides in the next product kernel).  Valid after mk_solver_setup. */
+MK_API int mk_solver_unapplied(const mk_solver *s, int64_t *count);
 /* Second per-iteration channel, same length as the history (MINRES: truncated direct-error
  * estimate / energy norm, `dir_errors_window` of minres.py:307-308; NaN while itn <= window). */
 MK_API int mk_solver_history2(const mk_solver *s, double *hist_host, int64_t cap);

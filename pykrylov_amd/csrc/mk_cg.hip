@@ -20,11 +20,21 @@
 // the bit of the three-kernel pass.  Traffic per pass: (48n read/write in K1f) + 24n instead of 16n + 24n + 40n: one
 // sweep over p less.  The update of the LAST pass is applied when the loop has halted (mk_solver_x / _vector / finish:
 // `materialize`); a caller that looks at x between passes gets x + alpha p formed into a scratch vector.
+//
+// DEFERRED x (MK_CG_XDEFER = m > 1): x is an accumulator that nothing in the loop reads, so K1f leaves it alone (p_old, r in;
+// p, Ap out) and the directions stay where the products wrote them, in a ring of m + 1 buffers (pass k writes slot
+// k % (m + 1)); K2 keeps alpha_k in a ring of the scalar file.  After every m-th pass -- and at the end of every
+// mk_solver_iterate call, before its closing event, so that a timed call contains the applications of its own passes --
+// `cg_xapply` sweeps x once: x = fl(x + fl(alpha_k p_k)) for the pending k in order, in registers, each step rounded on its
+// own: the bits of m sweeps.  x costs 16 n / m + 8 n bytes per pass instead of 16 n.
 #include "mk_solver.h"
 
 namespace {
 
-enum { S_RY0 = 0, S_RY1 = 1, S_THRESH = 2, S_RESID = 3, S_RESID0 = 4, S_PAP = 5, S_ALPHA = 6, S_BETA = 7, S_PENDING = 8 };
+enum { S_RY0 = 0, S_RY1 = 1, S_THRESH = 2, S_RESID = 3, S_RESID0 = 4, S_PAP = 5, S_ALPHA = 6, S_BETA = 7, S_PENDING = 8,
+       S_ARING = 32 };                                     // alpha of pass k at S_ARING + k % (m + 1) (deferred x)
+constexpr int MK_XD_MAX = 32;                              // cap of MK_CG_XDEFER
+static_assert(S_ARING + MK_XD_MAX + 1 <= MK_NSCAL, "the alpha ring lives in the scalar file");
 
 template <bool NTY>
 struct CgSpmvEpiT {
@@ -63,15 +73,17 @@ struct CgSpmvEpiT {
 };
 using CgSpmvEpi = CgSpmvEpiT<false>;
 
-// K1f: the brick march's "fuse" hooks (mk_spmv_fmt9.h).  Only ever launched on a format-9 matrix; the other formats'
-// instantiations exist because the launcher is generic and are never run.
+// K1f: the brick march's "fuse" hooks (mk_spmv_fmt9.h).  Only ever launched on a plain march matrix (formats 9 / 10 / 11):
+// MARCH_ONLY keeps the generic launcher from compiling any other kernel for them.
 #ifndef MK_FUSE_NT_DEF
 #define MK_FUSE_NT_DEF 7                                     // 1 nt loads of x, 2 nt stores of x, 4 nt stores of the new p (profiles/r05_fuse_nt_ab.txt: all three)
 #endif
-template <bool NTY>
+template <bool NTY, bool FX = true>
 struct CgFusedEpiT {
     static constexpr int NACC = 1, SLOT0 = 0;
     static constexpr bool SYM_MARCH = true;
+    static constexpr bool FUSE_X = FX;                       // false: x stays out of the kernel (deferred, cg_xapply)
+    static constexpr bool MARCH_ONLY = true;                 // only the march kernels are compiled for it (mk_device.h)
     static constexpr int FUSE_NT = NTY ? MK_FUSE_NT_DEF : 0;  // vectors beyond the Infinity Cache: x / the new p past the caches too
     double *Ap;
     const double *fuse_r;
@@ -135,9 +147,66 @@ __global__ __launch_bounds__(MK_BLOCK) void cg_flush_kernel(int64_t n, const dou
     const bool pend = scal[S_PENDING] != 0.0;
     const double alpha = scal[S_ALPHA], beta = scal[S_BETA];
     for (int64_t i = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MK_BLOCK) {
-        const double pv = p[i], xv = x[i];
-        x_out[i] = pend ? xv + alpha * pv : xv;           // cg.py:130
+        const double pv = p[i];
+        if (x_out) {                                      // (null: x is deferred, cg_xapply has it)
+            const double xv = x[i];
+            x_out[i] = pend ? xv + alpha * pv : xv;       // cg.py:130
+        }
         p_out[i] = pend ? beta * pv - r[i] : pv;          // cg.py:150-151
+    }
+}
+
+// Deferred x: x += alpha_k p_k (cg.py:130) for the passes k in [lo, hi) in order, one sweep over x, 16 bytes per lane.  `hi` is
+// what the host enqueued; the passes the DEVICE completed decide (st->itn: a pass stopped by the curvature test applies
+// nothing, cg.py:119-124, and passes enqueued behind a halt never ran).  Outside the halt protocol: it reads only what no
+// concurrent workgroup writes, and a range that was applied is never asked for again (the host's `x_applied`).
+struct CgXRing {
+    const double *p[MK_XD_MAX + 1];
+};
+template <bool NT>
+__device__ __forceinline__ mk_d2 cg_ld2(const double *v, int64_t i) {
+    if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const mk_d2 *>(v + i));
+    else return *reinterpret_cast<const mk_d2 *>(v + i);
+}
+template <bool NT>
+__global__ __launch_bounds__(MK_BLOCK) void cg_xapply_kernel(int64_t n, const double *scal, const MkStatus *st, CgXRing ring, int R,
+                                                             int64_t lo, int64_t hi, double *x) {
+    const int64_t done = st->itn;
+    if (hi > done) hi = done;
+    if (lo >= hi) return;
+    const int64_t S = (int64_t)gridDim.x * MK_BLOCK, g = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x, npair = n >> 1;
+    for (int64_t q = g; q < npair; q += S) {
+        mk_d2 xv = cg_ld2<NT>(x, 2 * q);
+        int64_t k = lo;
+        for (; k + 4 <= hi; k += 4) {                     // four directions in flight (uniform trip counts)
+            mk_d2 pv[4];
+            double a[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int s = (int)((k + u) % R);
+                pv[u] = cg_ld2<NT>(ring.p[s], 2 * q);
+                a[u] = scal[S_ARING + s];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                xv.x = xv.x + a[u] * pv[u].x;
+                xv.y = xv.y + a[u] * pv[u].y;
+            }
+        }
+        for (; k < hi; ++k) {
+            const int s = (int)(k % R);
+            const mk_d2 pv = cg_ld2<NT>(ring.p[s], 2 * q);
+            const double a = scal[S_ARING + s];
+            xv.x = xv.x + a * pv.x;
+            xv.y = xv.y + a * pv.y;
+        }
+        if constexpr (NT) __builtin_nontemporal_store(xv, reinterpret_cast<mk_d2 *>(x + 2 * q));
+        else *reinterpret_cast<mk_d2 *>(x + 2 * q) = xv;
+    }
+    if ((n & 1) && g == (npair % S)) {
+        double xv = x[n - 1];
+        for (int64_t k = lo; k < hi; ++k) xv = xv + scal[S_ARING + (int)(k % R)] * ring.p[(int)(k % R)][n - 1];
+        x[n - 1] = xv;
     }
 }
 
@@ -155,6 +224,7 @@ struct CgUpdateR {
     bool bad;
     MkTotalRegs tr;
     double ry_in;
+    double *aslot = nullptr;                              // deferred x: where alpha of this pass is kept for cg_xapply
     __device__ void early() {
         mk_total_issue(part, np, tr);
         ry_in = scal[S_RY0 + par];
@@ -168,6 +238,7 @@ struct CgUpdateR {
             st->nMatvec += 1;                             // cg.py:116
             scal[S_PAP] = pAp;
             scal[S_ALPHA] = alpha;
+            if (aslot) *aslot = alpha;
             if (bad) st->definite = 0;
         }
         return bad;
@@ -291,11 +362,16 @@ struct CgSolver : mk_solver {
     double *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_Ap = nullptr;
     // fused passes (see the top of the file)
     bool fused = false;
-    double *d_p2 = nullptr, *d_dump = nullptr;            // the second p buffer; the dump rows of the brick march
+    double *d_dump = nullptr;                             // the dump rows of the brick march
+    // the direction buffers: ring[0] = d_p; fused passes use the first m + 1 (m = xdefer; 1: the pair that alternates).  Each has
+    // nx entries: a slab keeps the neighbours' planes of the direction behind the own rows
+    std::vector<double *> ring;
+    int xdefer = 1;                                       // m of this solve: x is swept once per m passes (1: inside K1f)
+    mutable int64_t x_applied = 0;                        // deferred x: directions [0, x_applied) have been asked to be applied
     mutable double *d_xv = nullptr, *d_pv = nullptr;      // the iterate / direction as a caller sees them between passes
     mutable bool flushed = false;
     int64_t nmv0 = 0;                                     // products before the loop (the initial guess's)
-    double *pbuf(int64_t k) const { return (!fused || (k & 1) == 0) ? d_p : d_p2; }     // p of pass k
+    double *pbuf(int64_t k) const { return fused ? ring[(size_t)(k % (xdefer + 1))] : d_p; }     // p of pass k
     // the buffer of the direction in use: product k WROTE pbuf(k), and the passes the host enqueued behind a halt never ran,
     // so the products the DEVICE counted decide (K2 counts one per product, cg.py:116), not the host's pass counter
     double *pcur() const {
@@ -312,6 +388,47 @@ struct CgSolver : mk_solver {
         const char *e = getenv("MK_CG_FUSE");              // (read at every setup: tests switch it between solves)
         return !e || atoi(e) != 0;
     }
+    // MK_CG_XDEFER = m (read at every setup like MK_CG_FUSE).  Unset: 8 where the vectors lie beyond the Infinity Cache -- the
+    // deferral saves HBM traffic and costs one kernel boundary per m passes, so a problem whose x stays in the cache has
+    // nothing to gain from it -- and 1 elsewhere.
+    int want_xdefer() const {
+        const char *e = getenv("MK_CG_XDEFER");
+        int m = e ? atoi(e) : (sizeof(double) * (size_t)n > ((size_t)256 << 20) ? 8 : 1);
+        return m < 1 ? 1 : (m > MK_XD_MAX ? MK_XD_MAX : m);
+    }
+    // grow the ring towards m + 1 buffers; returns the m it can serve (0: not even the pair of today's fused pass).  The buffers
+    // beyond the pair may take an eighth of the device memory that is free: a placement search holds several solvers at once.
+    int ring_reserve(int m) {
+        const size_t bytes = sizeof(double) * (size_t)nx;
+        while ((int)ring.size() < m + 1) {
+            if (ring.size() >= 2) {
+                const size_t extra = (ring.size() - 2) * bytes;
+                size_t fr = 0, tot = 0;
+                if (hipMemGetInfo(&fr, &tot) != hipSuccess || extra + bytes > (fr + extra) / 8) break;
+            }
+            double *v = nullptr;
+            if (alloc_vec(&v, nx) != MK_OK) {
+                (void)hipGetLastError();                     // (reported by the fall-back, not by the next launch check)
+                break;
+            }
+            ring.push_back(v);
+        }
+        const int got = (int)ring.size() - 1;
+        return got < m ? got : m;
+    }
+    // deferred x: enqueue the application of the directions [x_applied, hi) -- clamped on the device to the passes it completed
+    void enqueue_xapply(int64_t hi) const {
+        if (hi <= x_applied) return;
+        CgXRing rg{};
+        const int R = xdefer + 1;
+        for (int k = 0; k < R; ++k) rg.p[k] = ring[(size_t)k];
+        const int grid = mk_grid_stream(n);
+        if (mk_store_nt(A))
+            hipLaunchKernelGGL(cg_xapply_kernel<true>, dim3(grid), dim3(MK_BLOCK), 0, stream, n, d_scal, d_status, rg, R, x_applied, hi, d_x);
+        else
+            hipLaunchKernelGGL(cg_xapply_kernel<false>, dim3(grid), dim3(MK_BLOCK), 0, stream, n, d_scal, d_status, rg, R, x_applied, hi, d_x);
+        x_applied = hi;
+    }
     // apply (halted) or form (running) the pending x / p update; returns the vectors a caller may read
     void materialize(const double **xo, const double **po) const {
         CgSolver *me = const_cast<CgSolver *>(this);
@@ -320,27 +437,49 @@ struct CgSolver : mk_solver {
         *po = pc;
         if (!fused || it == 0 || !is_setup) return;
         const int grid = (int)((n + MK_BLOCK - 1) / MK_BLOCK > 2048 ? 2048 : (n + MK_BLOCK - 1) / MK_BLOCK);
+        // deferred x: whatever is still to be applied goes into x itself, running or halted -- x is an accumulator the loop never
+        // reads, and every direction is applied once, in order (after an iterate call nothing is left: `drain`)
+        const bool defer = xdefer > 1;
+        if (defer) enqueue_xapply(it);
         if (halted) {
             if (!flushed) {
-                hipLaunchKernelGGL(cg_flush_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, n, d_scal, d_r, pc, d_x, pc, d_x);
+                hipLaunchKernelGGL(cg_flush_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, n, d_scal, d_r, pc, d_x, pc, defer ? nullptr : d_x);
                 hipMemsetAsync(d_scal + S_PENDING, 0, sizeof(double), stream);
                 me->flushed = true;
             }
             return;
         }
-        if (!d_xv && (me->alloc_vec(&me->d_xv, n) != MK_OK || me->alloc_vec(&me->d_pv, n) != MK_OK)) return;
-        hipLaunchKernelGGL(cg_flush_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, n, d_scal, d_r, pc, d_x, d_pv, d_xv);
-        *xo = d_xv;
+        if (!d_pv && me->alloc_vec(&me->d_pv, n) != MK_OK) return;
+        if (!defer && !d_xv && me->alloc_vec(&me->d_xv, n) != MK_OK) return;
+        hipLaunchKernelGGL(cg_flush_kernel, dim3(grid), dim3(MK_BLOCK), 0, stream, n, d_scal, d_r, pc, d_x, d_pv, defer ? nullptr : d_xv);
+        if (!defer) *xo = d_xv;
         *po = d_pv;
+    }
+    int drain() override {                                  // end of an iterate call: the applications of its own passes
+        if (fused && xdefer > 1) enqueue_xapply(it);
+        return MK_OK;
+    }
+    int64_t unapplied() const override {                    // completed passes (as of the last poll) whose direction is not in x yet
+        if (!fused || !is_setup) return 0;
+        if (xdefer > 1) return h_status->itn > x_applied ? h_status->itn - x_applied : 0;
+        return (h_scal[S_PENDING] != 0.0 && !flushed) ? 1 : 0;
     }
 
     int setup(const double *rhs, const double *guess) override {
-        if (!d_x) {
-            int rc;
-            // (r with room for received entries too: fused passes on a slab exchange r's boundary planes, not p's)
-            if ((rc = alloc_vec(&d_x, nx)) || (rc = alloc_vec(&d_r, nx)) || (rc = alloc_vec(&d_p, nx)) ||
-                (rc = alloc_vec(&d_Ap, n)))
-                return rc;
+        int rc_alloc = MK_OK;
+        // (r with room for received entries too: fused passes on a slab exchange r's boundary planes, not p's; each vector is
+        //  allocated where it is still missing: a set-up that failed half way is repeated from where it stopped)
+        if (!d_x) rc_alloc = alloc_vec(&d_x, nx);
+        if (rc_alloc == MK_OK && !d_r) rc_alloc = alloc_vec(&d_r, nx);
+        if (rc_alloc == MK_OK && !d_p && (rc_alloc = alloc_vec(&d_p, nx)) == MK_OK) ring.assign(1, d_p);
+        if (rc_alloc == MK_OK && !d_Ap) rc_alloc = alloc_vec(&d_Ap, n);
+        if (rc_alloc != MK_OK) {
+            // the other ranks are on their way into the veto all-reduce below: vote before leaving
+            if (mk_comm_active()) {
+                double veto = 1.0;
+                mk_comm_allreduce_host(&veto, 1);
+            }
+            return rc_alloc;
         }
         const MkPlan *plan = A ? mk_csr_plan(A) : nullptr;
         // one device, or one rank's slab under a halo exchange (the march takes the neighbours' planes from the received entries)
@@ -348,7 +487,20 @@ struct CgSolver : mk_solver {
         fused = want_fuse() && plan && mk_fmt_march(plan->fmt) && !precon_fn && A->nops == 0 && !A->comp_kind &&
                 ((!mk_comm_active() && A->ex.mode < 0 && nx == n) || slab);
         flushed = false;
-        if (fused && !d_p2 && (alloc_vec(&d_p2, nx) != MK_OK || alloc_vec(&d_dump, (int64_t)MK_MAXP * 1024) != MK_OK)) fused = false;
+        x_applied = 0;
+        xdefer = 1;
+        if (fused && !d_dump && alloc_vec(&d_dump, (int64_t)MK_MAXP * 1024) != MK_OK) {
+            (void)hipGetLastError();
+            d_dump = nullptr;
+            fused = false;
+        }
+        if (fused) {
+            xdefer = ring_reserve(want_xdefer());           // (a ring that cannot be had: a smaller m, down to today's pair)
+            if (xdefer < 1) {
+                xdefer = 1;
+                fused = false;
+            }
+        }
         if (mk_comm_active()) {
             // The choice changes what travels: fused ranks exchange r's boundary planes and form the neighbours' p themselves,
             // the others exchange p -- messages of the same size, so a disagreement would neither hang nor fail, it would
@@ -389,16 +541,31 @@ struct CgSolver : mk_solver {
     int enqueue_spmv_only(int which) override {
         if (which != 0) return mk_fail(MK_ERR_ARG, "CG has one product per pass");
         if (fused && it > 0) {
-            // the fused kernel exactly as a pass launches it (same streams: p_old, r, x in; p, x, Ap out), except that p goes
-            // to the buffer it came from's twin and x is updated again with the same alpha -- timing only, after the run
-            double *pc = pcur(), *po = (pc == d_p) ? d_p2 : d_p;
-            if (mk_store_nt(A)) mk_launch_spmv(this, pc, CgFusedEpiT<true>{d_Ap, d_r, d_x, po, d_dump, d_scal, 0.0, 0.0}, false);
-            else mk_launch_spmv(this, pc, CgFusedEpiT<false>{d_Ap, d_r, d_x, po, d_dump, d_scal, 0.0, 0.0}, false);
+            // the fused kernel exactly as a pass launches it (same streams: p_old, r in; p, Ap out; with m = 1 x in and out too,
+            // updated again with the same alpha), except that p goes to the ring slot behind the one it came from -- after an
+            // iterate call every direction has been applied (`drain`), so no slot holds one that x still needs -- timing
+            // only, after the run
+            double *pc = pcur(), *po = ring[0];
+            for (int k = 0; k <= xdefer; ++k)
+                if (ring[(size_t)k] == pc) po = ring[(size_t)((k + 1) % (xdefer + 1))];
+            launch_fused(pc, po, false);
             return MK_OK;
         }
         if (A && mk_store_nt(A)) mk_launch_spmv(this, d_p, CgSpmvEpiT<true>{d_p, d_Ap, 0.0}, false);
         else mk_launch_spmv(this, d_p, CgSpmvEpi{d_p, d_Ap, 0.0}, false);
         return MK_OK;
+    }
+
+    // K1f on p_old = `po`, the new p into `pn`: with x (m = 1) or without (deferred)
+    void launch_fused(const double *po, double *pn, bool timed) {
+        const bool nt = mk_store_nt(A);
+        if (xdefer > 1) {
+            if (nt) mk_launch_spmv(this, po, CgFusedEpiT<true, false>{d_Ap, d_r, d_x, pn, d_dump, d_scal, 0.0, 0.0}, timed);
+            else mk_launch_spmv(this, po, CgFusedEpiT<false, false>{d_Ap, d_r, d_x, pn, d_dump, d_scal, 0.0, 0.0}, timed);
+        } else {
+            if (nt) mk_launch_spmv(this, po, CgFusedEpiT<true>{d_Ap, d_r, d_x, pn, d_dump, d_scal, 0.0, 0.0}, timed);
+            else mk_launch_spmv(this, po, CgFusedEpiT<false>{d_Ap, d_r, d_x, pn, d_dump, d_scal, 0.0, 0.0}, timed);
+        }
     }
 
     int enqueue_pass() override {
@@ -415,15 +582,18 @@ struct CgSolver : mk_solver {
                 // of the p buffers since the pass before) and their r -- so it is r whose boundary planes travel, as soon as K2 of
                 // the pass before has written them; the interior planes' launch overlaps the messages as everywhere
                 if ((rc = exchange(d_r)) != MK_OK) return rc;
-                if (nt) mk_launch_spmv(this, pbuf(it - 1), CgFusedEpiT<true>{d_Ap, d_r, d_x, pbuf(it), d_dump, d_scal, 0.0, 0.0});
-                else mk_launch_spmv(this, pbuf(it - 1), CgFusedEpiT<false>{d_Ap, d_r, d_x, pbuf(it), d_dump, d_scal, 0.0, 0.0});
+                launch_fused(pbuf(it - 1), pbuf(it), true);
             }
             if ((rc = allreduce(0, 1)) != MK_OK) return rc;
-            mk_launch_stream(this, CgUpdateR{d_part, np_spmv, d_scal, d_status, par, prm.check_curvature, d_Ap, d_r,
-                                             d_prec, 0.0, false}, n);
+            CgUpdateR k2{d_part, np_spmv, d_scal, d_status, par, prm.check_curvature, d_Ap, d_r, d_prec, 0.0, false};
+            if (xdefer > 1) k2.aslot = d_scal + S_ARING + (int)(it % (xdefer + 1));
+            mk_launch_stream(this, k2, n);
             if ((rc = allreduce(1, 1)) != MK_OK) return rc;
             hipLaunchKernelGGL(cg_beta_kernel, dim3(1), dim3(MK_BLOCK), 0, stream, d_part, np_stream, d_scal, d_status, d_hist,
                                par, prm.matvec_max, next_halt());
+            // deferred x: pass `it` has put the m-th direction into the ring -- one sweep over x applies them, before pass
+            // it + 1 writes the slot of the oldest
+            if (xdefer > 1 && it + 1 - x_applied >= xdefer) enqueue_xapply(it + 1);
             return MK_OK;
         }
         rc = exchange(d_p);

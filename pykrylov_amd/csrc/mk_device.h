@@ -471,6 +471,13 @@ template <class Epi, class = void>
 struct MkNoMarch : std::false_type {};
 template <class Epi>
 struct MkNoMarch<Epi, std::enable_if_t<Epi::NO_MARCH>> : std::true_type {};
+// `static constexpr bool MARCH_ONLY = true`: an epilogue that exists for the brick march alone (CG's fuse hooks, mk_cg.hip: the
+// solver launches it on a plain march matrix and nowhere else) -- only the six march kernels are compiled for it, without a row
+// program and without the wrappers of composed / column-blocked / matrix-free products; a launch on anything else is an error.
+template <class Epi, class = void>
+struct MkMarchOnly : std::false_type {};
+template <class Epi>
+struct MkMarchOnly<Epi, std::enable_if_t<Epi::MARCH_ONLY>> : std::true_type {};
 template <class Epi, class = void>
 struct MkSymMarch : std::false_type {};
 template <class Epi>
@@ -796,7 +803,14 @@ static inline void mk_spmv_launch_fmt(const MkCsrView &v, int grid, hipStream_t 
         const size_t w = sizeof(double) * (size_t)(128 * v.wchunks + 2) + sizeof(uint32_t) * (MK_SPMV_TILE + 16);
         lds = w > lds ? w : lds;
     }
-    if (mk_fmt_march(v.fmt) && (MkNoMarch<Epi>::value || ((v.fmt == 11 || v.pen_gen == 2) && !MkSymMarch<Epi>::value))) {
+    if constexpr (MkMarchOnly<Epi>::value) {
+        static_assert(MkSymMarch<Epi>::value && !MkNoMarch<Epi>::value && !PROG, "a march-only epilogue has all six march kernels and no row program");
+        if (!mk_fmt_march(v.fmt)) {
+            const int rc = mk_fail(MK_ERR_STATE, "a march-only product kernel was launched on storage format %d", v.fmt);
+            if (mk_ctx().pending_rc == MK_OK) mk_ctx().pending_rc = rc;
+            return;
+        }
+    } else if (mk_fmt_march(v.fmt) && (MkNoMarch<Epi>::value || ((v.fmt == 11 || v.pen_gen == 2) && !MkSymMarch<Epi>::value))) {
         MkCsrView w = v;                                     // (see MkNoMarch: a format forced by hand on a loop that has no such kernel)
         w.fmt = 0;
         hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, 0>), dim3(grid), dim3(MK_BLOCK), lds, st, w, x, epi, gate, halt, partials);
@@ -838,6 +852,7 @@ static inline void mk_spmv_launch_fmt(const MkCsrView &v, int grid, hipStream_t 
         }
         return;
     }
+    if constexpr (!MkMarchOnly<Epi>::value) {
     if (v.fmt == 4) {                                        // windows + pattern table, or the gather path's products
         size_t wtop = (size_t)(128 * v.wchunks + 2);
         if (!v.allwin && wtop < (size_t)MK_PROD_LDS) wtop = (size_t)MK_PROD_LDS;
@@ -884,14 +899,19 @@ static inline void mk_spmv_launch_fmt(const MkCsrView &v, int grid, hipStream_t 
     else
         hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, 0>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi, gate,
                            halt, partials);
+    }
 }
 
 template <class Epi, class Gate>
 static inline void mk_spmv_launch_view(const MkCsrView &v, int grid, hipStream_t st, const double *x, const Epi &epi,
                                        const Gate &gate, MkHalt halt, double *partials) {
     if (grid < 1) grid = 1;                                  // (a launch never vanishes: every kernel hands the halt word on)
-    if (v.nops > 0) mk_spmv_launch_fmt<Epi, Gate, true>(v, grid, st, x, epi, gate, halt, partials);
-    else mk_spmv_launch_fmt<Epi, Gate, false>(v, grid, st, x, epi, gate, halt, partials);
+    if constexpr (MkMarchOnly<Epi>::value) {                 // (no row program: mk_spmv_launch_blocks has checked)
+        mk_spmv_launch_fmt<Epi, Gate, false>(v, grid, st, x, epi, gate, halt, partials);
+    } else {
+        if (v.nops > 0) mk_spmv_launch_fmt<Epi, Gate, true>(v, grid, st, x, epi, gate, halt, partials);
+        else mk_spmv_launch_fmt<Epi, Gate, false>(v, grid, st, x, epi, gate, halt, partials);
+    }
 }
 
 // Column-blocked product (mk_format.hip): the matrix is stored as K column blocks, each a CSR matrix over all rows.
@@ -966,6 +986,16 @@ struct MkNoXin : MkWrapBase<Epi> {   // the outer product of `A*(B*x)`: its inpu
 template <class Epi, class Gate, class HaltSrc>
 static inline void mk_spmv_launch_blocks(const mk_csr *A, int grid, hipStream_t st, const double *x, const Epi &epi,
                                          const Gate &gate, HaltSrc &&next, double *partials) {
+    if constexpr (MkMarchOnly<Epi>::value) {                 // a plain march matrix, one launch -- or an error (see MkMarchOnly)
+        const MkPlan *P = mk_csr_plan(A);
+        if (A->comp_kind || A->host_fn || A->nops > 0 || !P || !mk_fmt_march(P->fmt)) {
+            const int rc = mk_fail(MK_ERR_STATE, "a march-only product kernel was launched on an operator that is no plain march matrix");
+            if (mk_ctx().pending_rc == MK_OK) mk_ctx().pending_rc = rc;
+            return;
+        }
+        mk_spmv_launch_view(mk_view(A), grid, st, x, epi, gate, next(), partials);
+        return;
+    } else {
     if (A->comp_kind == 5) {
         // Restriction of a device matrix: scatter x into a zero vector of the base's width, the base's complete product
         // (gate with its side effects; the epilogue's on-the-fly scaling applies to the scattered entries), gather the
@@ -1112,6 +1142,7 @@ static inline void mk_spmv_launch_blocks(const mk_csr *A, int grid, hipStream_t 
         } else {
             mk_spmv_launch_view(v, grid, st, x, epi, gate, next(), partials);
         }
+    }
     }
 }
 

@@ -97,6 +97,10 @@ struct mk_solver {
     virtual const double *vector(int) const { return nullptr; }
     virtual bool takes_precon() const { return false; }
     virtual bool is_fused() const { return false; }   // CG on a format-9 matrix: the x / p update rides in the next product kernel
+    // work a loop defers beyond its passes (CG: the x update over a ring of directions): `drain` enqueues what is applicable at
+    // the end of an iterate call, inside its timed region; `unapplied` counts completed passes whose update is still missing
+    virtual int drain() { return MK_OK; }
+    virtual int64_t unapplied() const { return 0; }
     // enqueue only the solver's (fused) SpMV kernel, exactly as a loop pass launches it; used to time
     // that kernel back to back.  Overwrites the product vector and its partial sums.
     // `which`: 0 = the first product of a pass, 1 = the second (BiCGSTAB / CGS / TFQMR: the product on z; least squares:

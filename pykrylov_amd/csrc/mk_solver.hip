@@ -260,6 +260,10 @@ int mk_solver::iterate(int64_t max_iters, int64_t *done) {
         if (rc != MK_OK) return rc;
         if (batch < MK_BATCH_MAX) batch *= 2;
     }
+    {   // what the passes of this call deferred runs inside the call, before its closing event
+        const int rc = drain();
+        if (rc != MK_OK) return rc;
+    }
     MK_HIP(hipEventRecord(ev1, stream));
     MK_HIP(hipEventSynchronize(ev1));
     float ms = 0.f;
@@ -527,6 +531,12 @@ extern "C" int mk_solver_x(const mk_solver *s, const double **x_dev) {
 extern "C" int mk_solver_fused(const mk_solver *s, int32_t *fused) {
     MK_ARG(s && fused);
     *fused = s->is_fused() ? 1 : 0;
+    return MK_OK;
+}
+
+extern "C" int mk_solver_unapplied(const mk_solver *s, int64_t *count) {
+    MK_ARG(s && count);
+    *count = s->unapplied();
     return MK_OK;
 }
 

@@ -54,6 +54,12 @@ template <class Epi, class = void>
 struct MkHasFuse : std::false_type {};
 template <class Epi>
 struct MkHasFuse<Epi, std::void_t<decltype(std::declval<Epi &>().fuse_r)>> : std::true_type {};
+// A fuse hook set with `static constexpr bool FUSE_X = false` leaves x out (CG with a deferred x update, mk_cg.hip): no x
+// loads, no `xx` ring, no fuse_xnew, no x stores -- p_old and r in, p and the product out.
+template <class Epi, class = void>
+struct MkFuseX : std::true_type {};
+template <class Epi>
+struct MkFuseX<Epi, std::void_t<decltype(Epi::FUSE_X)>> : std::bool_constant<Epi::FUSE_X> {};
 
 // GENERAL GEOMETRY (round 6; template flag GEN).  The march above needs L % 128 == 0, P % 4L == 0: bricks tile the plane and every
 // pair of rows starts at a 16-byte boundary.  GEN lifts both: a plane of P rows is cut into lines of L rows (the last one may be
@@ -138,6 +144,7 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
     static_assert(MK_PEN_R == 6, "mk_pen_split (mk_device.h) cuts a slab's boundary planes in rounds of 6");
     constexpr bool ROWX = !PROG && MkHasRowX<Epi>::value;
     constexpr bool FUSE = MkHasFuse<Epi>::value;
+    constexpr bool FUSEX = FUSE && MkFuseX<Epi>::value;      // the deferred x update rides along
     constexpr int FNT = [] { if constexpr (MkHasFuse<Epi>::value) return (int)Epi::FUSE_NT; else return 0; }();
     // epilogue operands loaded at the top of a step (mk_device.h: row_pf / row_x_pf)
     constexpr bool XPF = !PROG && MkHasRowXPf<Epi>::value;
@@ -242,7 +249,7 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
         unsigned pidr[H];
         [[maybe_unused]] double hvr[SYM ? H : 1], evr[SYM ? H : 1];     // SYM: +L values of the halo line below, +1 values of the west edge rows
         [[maybe_unused]] double hr[FUSE ? H : 1], er[FUSE ? H : 1];      // fuse: r at the halo rows
-        [[maybe_unused]] mk_d2 rr[FUSE ? H : 1], xx[FUSE ? H : 1];      // fuse: r and x at the own rows of the plane to transform next
+        [[maybe_unused]] mk_d2 rr[FUSE ? H : 1], xx[FUSEX ? H : 1];     // fuse: r and x at the own rows of the plane to transform next
         auto halo = [&](int p, int d) {                       // plane p at the halo rows + the pattern bytes of the own rows
             p = p > nz - 1 ? nz - 1 : p;
             hreg[d] = x[clampr((int64_t)p * P + hc)];
@@ -279,9 +286,11 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
                 if (store) {                                 // (compile-time constant at every call site of the pipelined loop)
                     const bool own = pl >= z0 && pl < z1;    // (workgroup uniform: a scalar select of the address)
                     double *dump = epi.fuse_dump + (int64_t)blockIdx.x * 1024 + 2 * tid;
-                    mk_d2 xn;
-                    xn.x = epi.fuse_xnew(xv.x, po.x);
-                    xn.y = epi.fuse_xnew(xv.y, po.y);
+                    [[maybe_unused]] mk_d2 xn{0.0, 0.0};
+                    if constexpr (FUSEX) {
+                        xn.x = epi.fuse_xnew(xv.x, po.x);
+                        xn.y = epi.fuse_xnew(xv.y, po.y);
+                    }
                     if constexpr (GEN) {
                         // the same targets; a lane writes its pair where both rows exist, a row alone where only the first does
                         // (odd L or P: divergent, rare), nothing otherwise; `lv`: the step is one of the chunk's own (not a
@@ -290,16 +299,20 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
                         pt = (pl == -1 && A.pen_xlo >= 0) ? epi.fuse_p + off_lo + c : pt;
                         pt = (pl == nz && A.pen_xhi >= 0) ? epi.fuse_p + off_hi + c : pt;
                         pt = lv ? pt : nullptr;
-                        double *xt = (own && lv) ? epi.fuse_x + (int64_t)pl * P + c : nullptr;
                         mk_d2u *pd = reinterpret_cast<mk_d2u *>((pt && okb) ? pt : dump);
-                        mk_d2u *xd = reinterpret_cast<mk_d2u *>((xt && okb) ? xt : dump + 512);
                         if constexpr (FNT & 4) __builtin_nontemporal_store(pv, pd);
                         else *pd = pv;
-                        if constexpr (FNT & 2) __builtin_nontemporal_store(xn, xd);
-                        else *xd = xn;
-                        if (oka && !okb) {
-                            if (pt) *pt = pv.x;
-                            if (xt) *xt = xn.x;
+                        if constexpr (FUSEX) {
+                            double *xt = (own && lv) ? epi.fuse_x + (int64_t)pl * P + c : nullptr;
+                            mk_d2u *xd = reinterpret_cast<mk_d2u *>((xt && okb) ? xt : dump + 512);
+                            if constexpr (FNT & 2) __builtin_nontemporal_store(xn, xd);
+                            else *xd = xn;
+                            if (oka && !okb) {
+                                if (pt) *pt = pv.x;
+                                if (xt) *xt = xn.x;
+                            }
+                        } else {
+                            if (oka && !okb && pt) *pt = pv.x;
                         }
                         return;
                     }
@@ -310,9 +323,11 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
                     pd = (pl == nz && A.pen_xhi >= 0) ? epi.fuse_p + off_hi + c : pd;
                     if constexpr (FNT & 4) __builtin_nontemporal_store(pv, reinterpret_cast<mk_d2 *>(pd));
                     else *reinterpret_cast<mk_d2 *>(pd) = pv;
-                    mk_d2 *xd = reinterpret_cast<mk_d2 *>(own ? epi.fuse_x + (int64_t)pl * P + c : dump + 512);
-                    if constexpr (FNT & 2) __builtin_nontemporal_store(xn, xd);
-                    else *xd = xn;
+                    if constexpr (FUSEX) {
+                        mk_d2 *xd = reinterpret_cast<mk_d2 *>(own ? epi.fuse_x + (int64_t)pl * P + c : dump + 512);
+                        if constexpr (FNT & 2) __builtin_nontemporal_store(xn, xd);
+                        else *xd = xn;
+                    }
                 }
             }
         };
@@ -482,7 +497,7 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
             if constexpr (FUSE) {                             // r (and x) of the two planes the ring starts with
                 rm1 = plane_of(epi.fuse_r, z0 - 1);
                 r00 = plane_of(epi.fuse_r, z0);
-                x00 = plane_of_x(epi.fuse_x, z0);
+                if constexpr (FUSEX) x00 = plane_of_x(epi.fuse_x, z0);
             }
 #pragma unroll
             for (int d = 0; d < R - 1; ++d) {                 // (issue order = consumption order; slot R - 1 is loaded by step 0)
@@ -492,7 +507,7 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
                 if constexpr (FUSE) {
                     if (d < H) {                              // plane z0 + 1 + d -> slot (1 + d) % H
                         rr[(1 + d) % H] = plane_of(epi.fuse_r, z0 + 1 + d);
-                        xx[(1 + d) % H] = plane_of_x(epi.fuse_x, z0 + 1 + d);
+                        if constexpr (FUSEX) xx[(1 + d) % H] = plane_of_x(epi.fuse_x, z0 + 1 + d);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -511,7 +526,8 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
                 for (int d = 0; d < R; ++d) {
                     const int zz = z + d;
                     [[maybe_unused]] const bool live = !GEN || zz < z1;
-                    if constexpr (FUSE) transform(ring[(d + 2) % R], rr[(d + 1) % H], xx[(d + 1) % H], zz + 1, true, live);
+                    if constexpr (FUSEX) transform(ring[(d + 2) % R], rr[(d + 1) % H], xx[(d + 1) % H], zz + 1, true, live);
+                    else if constexpr (FUSE) transform(ring[(d + 2) % R], rr[(d + 1) % H], rr[(d + 1) % H], zz + 1, true, live);
                     step(zz, (d & 1) * BUF, ring[d], ring[(d + 1) % R], ring[(d + 2) % R], halo_val(hreg[d % H], hr[FUSE ? d % H : 0]),
                          halo_val(ereg[d % H], er[FUSE ? d % H : 0]), pidr[d % H], vr[STREAM ? d % VD : 0], hvr[SYM ? d % H : 0],
                          evr[SYM ? d % H : 0], [&]() {
@@ -520,7 +536,7 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
                              halo(zz + H, d % H);
                              if constexpr (FUSE) {            // plane zz + 1 + H into the slot plane zz + 1 just left
                                  rr[(d + 1) % H] = plane_of(epi.fuse_r, zz + 1 + H);
-                                 xx[(d + 1) % H] = plane_of_x(epi.fuse_x, zz + 1 + H);
+                                 if constexpr (FUSEX) xx[(d + 1) % H] = plane_of_x(epi.fuse_x, zz + 1 + H);
                              }
                          }, [&]() { vals(zz + VD, d % VD); }, live);   // (values: their slot is free once the row sums are formed)
                 }
@@ -534,7 +550,11 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
                 // planes zz - 1 and zz are formed again from p_old and r (x was updated when they were written: not touched);
                 // a chunk without pipelined rounds writes its first plane here; plane zz + 1 is formed and written now
                 const mk_d2 ra = plane_of(epi.fuse_r, zz - 1), rb = plane_of(epi.fuse_r, zz), rc = plane_of(epi.fuse_r, zz + 1);
-                const mk_d2 xb = plane_of_x(epi.fuse_x, zz), xcn = plane_of_x(epi.fuse_x, zz + 1);
+                mk_d2 xb = rb, xcn = rc;                      // (no x in the kernel: never used)
+                if constexpr (FUSEX) {
+                    xb = plane_of_x(epi.fuse_x, zz);
+                    xcn = plane_of_x(epi.fuse_x, zz + 1);
+                }
                 if (zz == z0) transform(xm, ra, ra, zz - 1, true);   // (written only as a slab's neighbour plane, see above)
                 else transform(xm, ra, ra, zz - 1, false);
                 if (zz == z0) transform(xc, rb, xb, zz, true);

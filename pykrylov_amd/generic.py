@@ -401,6 +401,12 @@ class DeviceRun(object):
         _lib.check(self.lib.mk_solver_x(self.handle, ctypes.byref(p)))
         return _lib.download(p.value, self.n_x)
 
+    def unapplied(self):
+        """Completed passes whose direction has not reached x yet (CG with a deferred x update: 0 after every `iterate`)."""
+        c = ctypes.c_int64()
+        _lib.check(self.lib.mk_solver_unapplied(self.handle, ctypes.byref(c)))
+        return int(c.value)
+
     def vector(self, index):
         p, ln = ctypes.c_void_p(), ctypes.c_int64()
         _lib.check(self.lib.mk_solver_vector(self.handle, index, ctypes.byref(p), ctypes.byref(ln)))
