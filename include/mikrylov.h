@@ -480,6 +480,50 @@ MK_API int mk_ilu_download(const mk_ilu *F, double *values_host, int32_t *diag_h
  * reference until it is destroyed or the preconditioner is replaced.  Replaces a diagonal, matrix or callback
  * preconditioner; those setters replace it in turn.  NULL removes it.  Single GPU.  Call before mk_solver_setup. */
 MK_API int mk_solver_set_precon_ilu(mk_solver *s, const mk_ilu *F);
+/* Limited-memory BFGS operators resident in HBM (linop/lbfgs.py): two rings of `npairs` (s, y) columns of n doubles, the
+ * scalars ys_k = s_k.y_k, alpha_k and gamma in device memory, partial-sum slots of the object's own, and the Gram entries
+ * s_k.s_l, s_k.y_l cached when a pair is stored.  1 <= npairs <= MK_LBFGS_MAX_PAIRS, n >= 1 (MK_ERR_ARG otherwise);
+ * `scaling` != 0 scales the initial matrix by gamma = ys / y.y of the newest pair (lbfgs.py:116-120). */
+typedef struct mk_lbfgs mk_lbfgs;
+#define MK_LBFGS_MAX_PAIRS 64
+MK_API int mk_lbfgs_create(int64_t n, int32_t npairs, int32_t scaling, mk_lbfgs **out);
+/* Destroying an operator that solvers still hold (mk_solver_set_precon_lbfgs) is deferred until the last of them goes. */
+MK_API int mk_lbfgs_destroy(mk_lbfgs *F);
+/* lbfgs.py:70-87: the pair (device vectors of n doubles, copied) is rejected (*accepted = 0) when s.y <= threshold (the
+ * reference's default is 1e-20), else it overwrites column `insert`, which advances modulo npairs.  s.y, y.y, s.s and the
+ * dots of s with every column that stays come from one read of the pair per group of eight dots.  Synchronises. */
+MK_API int mk_lbfgs_store(mk_lbfgs *F, const double *s_dev, const double *y_dev, double threshold, int32_t *accepted);
+/* lbfgs.py:89-95: forget every pair. */
+MK_API int mk_lbfgs_restart(mk_lbfgs *F);
+/* out = H in, the inverse approximation by the two-loop recursion (lbfgs.py:97-127) on device vectors (in == out allowed):
+ * 2p + 1 launches for p stored pairs (p = 0: a copy, or nothing when in == out); alpha_k and beta are formed on the device
+ * in each launch's prologue from the previous launch's partial sums.  Enqueued on the library's stream. */
+MK_API int mk_lbfgs_apply(const mk_lbfgs *F, const double *in_dev, double *out_dev);
+/* The two halves of the compact forward product (lbfgs.py:188-254) around the small solve the caller makes:
+ *   forward_dots:    a[0:p] = (v / gamma) . s_k, a[p:2p] = v . y_k, pairs oldest to newest (2p doubles to the host);
+ *   forward_combine: out = v / gamma, then per pair out -= (b_i / gamma) s_k; out -= b_{p+i} y_k (in == out allowed).
+ * use_gamma = 0 takes gamma = 1.  Every dot is summed in the order of the library's streaming dot (mk_dot). */
+MK_API int mk_lbfgs_forward_dots(const mk_lbfgs *F, const double *in_dev, int32_t use_gamma, double *a_host);
+MK_API int mk_lbfgs_forward_combine(const mk_lbfgs *F, const double *in_dev, int32_t use_gamma, const double *coef_host,
+                                    double *out_dev);
+/* The cached scalars by ring slot (the stored pairs are the slots 0 .. count-1; other entries are NaN): ss[k * npairs + l] =
+ * s_k.s_l and sy[k * npairs + l] = s_k.y_l for k stored after l, ss[k * npairs + k] = s_k.s_k, ys[k] = s_k.y_k, yy[k] =
+ * y_k.y_k.  Any pointer may be NULL. */
+MK_API int mk_lbfgs_gram(const mk_lbfgs *F, double *ss_host, double *sy_host, double *ys_host, double *yy_host);
+/* info[k] for k < min(cap, MK_LBFGS_INFO_LEN): 0 n, 1 npairs, 2 scaling, 3 insert, 4 stored pairs, 5 launches of the last
+ * apply, 6 applies enqueued, 7 pairs accepted, 8 pairs rejected, 9 device bytes held, 10 column stride (doubles),
+ * 11 MK_LBFGS_MAX_PAIRS. */
+#define MK_LBFGS_INFO_LEN 12
+MK_API int mk_lbfgs_info(const mk_lbfgs *F, int64_t *info, int32_t cap);
+/* The rings to the host: slot k to row k of an (npairs, n) array.  Either may be NULL. */
+MK_API int mk_lbfgs_download(const mk_lbfgs *F, double *s_host, double *y_host);
+/* ... and the inverse operator as the preconditioner of the six square solvers, like mk_solver_set_precon_ilu: applied on
+ * the device at the sites of the callback, every launch obeying the loop's halt words; the solver holds a reference until
+ * it is destroyed or the preconditioner is replaced; replaces a diagonal, matrix, callback or factorization
+ * preconditioner, and those setters replace it in turn; NULL removes it.  Single GPU (MK_ERR_UNSUPPORTED when the
+ * solver's operator carries an exchange plan), MK_ERR_ARG on a size mismatch.  Call before mk_solver_setup.  A pair stored
+ * between two solves is seen by the next one. */
+MK_API int mk_solver_set_precon_lbfgs(mk_solver *s, const mk_lbfgs *F);
 /* The least-squares kinds take two preconditioners, applied by the reference as `u = M(Mu)` in the m-space and
  * `v = N(Nv)` in the n-space of the Golub-Kahan process (lls/lsqr.py:189-190,201-202,253-254,265-266 and the same
  * lines of lsmr.py, craig.py, craigmr.py): device arrays with the diagonals of M (nrows(A) entries) and N

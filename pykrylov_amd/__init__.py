@@ -17,5 +17,6 @@ from .cgs import CGS                                                            
 from .tfqmr import TFQMR                                                                        # noqa: F401
 from .minres import Minres                                                                      # noqa: F401
 from .symmlq import Symmlq                                                                      # noqa: F401
+from .lbfgs import InverseLBFGSOperator, LBFGSOperator, CompactLBFGSOperator                    # noqa: F401
 from . import lls                                                                               # noqa: F401
 from . import blkop                                                                             # noqa: F401

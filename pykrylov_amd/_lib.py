@@ -34,6 +34,7 @@ class MkRowOp(ctypes.Structure):
 
 
 MK_ILU_INFO_LEN = 12      # entries of mk_ilu_info (include/mikrylov.h)
+MK_LBFGS_INFO_LEN = 12    # entries of mk_lbfgs_info
 
 MK_ROW_SCALE, MK_ROW_ADD, MK_ROW_SUB, MK_ROW_RSUB, MK_ROWPROG_MAX = 1, 2, 3, 4, 4
 
@@ -137,6 +138,17 @@ PROTOTYPES = {
     "mk_ilu_info": (ctypes.c_int, [c_vp, P(c_i64), c_i32]),
     "mk_ilu_download": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mk_solver_set_precon_ilu": (ctypes.c_int, [c_vp, c_vp]),
+    "mk_lbfgs_create": (ctypes.c_int, [c_i64, c_i32, c_i32, P(c_vp)]),
+    "mk_lbfgs_destroy": (ctypes.c_int, [c_vp]),
+    "mk_lbfgs_store": (ctypes.c_int, [c_vp, c_vp, c_vp, c_f64, P(c_i32)]),
+    "mk_lbfgs_restart": (ctypes.c_int, [c_vp]),
+    "mk_lbfgs_apply": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mk_lbfgs_forward_dots": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp]),
+    "mk_lbfgs_forward_combine": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "mk_lbfgs_gram": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mk_lbfgs_info": (ctypes.c_int, [c_vp, P(c_i64), c_i32]),
+    "mk_lbfgs_download": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mk_solver_set_precon_lbfgs": (ctypes.c_int, [c_vp, c_vp]),
     "mk_solver_set_lls_precon_callback": (ctypes.c_int, [c_vp, PRECON_FN, c_vp, PRECON_FN, c_vp]),
     "mk_solver_set_lls_precon": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mk_solver_setup": (ctypes.c_int, [c_vp, c_vp, c_vp]),

@@ -37,6 +37,13 @@ int64_t mk_ilu_rows(const mk_ilu *F);
 void mk_ilu_hold(const mk_ilu *F);
 void mk_ilu_release(const mk_ilu *F);
 
+// Inverse L-BFGS operator (mk_lbfgs.hip): out = H in on `stream` by the two-loop recursion (in == out allowed), the same
+// halt-word protocol and hold / release as the factorizations above.
+int mk_lbfgs_enqueue(const mk_lbfgs *F, const double *in, double *out, hipStream_t stream, int *flags, int64_t *q);
+int64_t mk_lbfgs_rows(const mk_lbfgs *F);
+void mk_lbfgs_hold(const mk_lbfgs *F);
+void mk_lbfgs_release(const mk_lbfgs *F);
+
 struct mk_solver {
     const mk_csr *A = nullptr;
     const mk_csr *At = nullptr;     // transposed matrix (least-squares solvers only)
@@ -54,6 +61,8 @@ struct mk_solver {
     // ... or through an incomplete factorization (mk_solver_set_precon_ilu: ILU(0) / IC(0)): two level-scheduled triangular
     // sweeps on the device at the same sites, in place
     const mk_ilu *precon_ilu = nullptr;
+    // ... or through an inverse L-BFGS operator (mk_solver_set_precon_lbfgs): the two-loop recursion at the same sites
+    const mk_lbfgs *precon_lbfgs = nullptr;
     int *d_nohalt = nullptr;        // two zero words: the halt input of a product that must run after the loop has ended
     int host_precon(const double *in_dev, double *out_dev, bool force = false);   // out = precon * in ; unless `force`, a no-op once the loop has halted
     mk_params prm{};

@@ -44,6 +44,12 @@ int mk_solver::host_precon(const double *in_dev, double *out_dev, bool force) {
                              : mk_ilu_enqueue(precon_ilu, in_dev, out_dev, stream, d_halt, &q);
         return rc != MK_OK ? rc : mk_ctx().pending_rc;
     }
+    if (precon_lbfgs) {
+        // out = H in by the chain of the two-loop recursion, under the same halt words
+        const int rc = force ? mk_lbfgs_enqueue(precon_lbfgs, in_dev, out_dev, stream, nullptr, nullptr)
+                             : mk_lbfgs_enqueue(precon_lbfgs, in_dev, out_dev, stream, d_halt, &q);
+        return rc != MK_OK ? rc : mk_ctx().pending_rc;
+    }
     if (precon_op) {
         // out = precon_op * in on the device.  Like every kernel of the loop the product obeys the halt words: once the
         // loop condition has failed it is a no-op, exactly when the reference applies nothing more -- unless `force`.
@@ -78,6 +84,7 @@ mk_solver::~mk_solver() {
     if (mk_ctx().ready) hipStreamSynchronize(mk_ctx().stream);
     if (precon_op) mk_release_operand(precon_op);
     if (precon_ilu) mk_ilu_release(precon_ilu);
+    if (precon_lbfgs) mk_lbfgs_release(precon_lbfgs);
     if (At) mk_release_operand(At);
     if (A && counted_user) mk_csr_count_users(A, -1);
     if (A) mk_release_operand(A);
@@ -349,6 +356,11 @@ extern "C" int mk_solver_set_precon_diag(mk_solver *s, const double *diag) {
         s->precon_ilu = nullptr;
         s->precon_fn = nullptr;
     }
+    if (s->precon_lbfgs) {                                   // ... and an L-BFGS operator
+        mk_lbfgs_release(s->precon_lbfgs);
+        s->precon_lbfgs = nullptr;
+        s->precon_fn = nullptr;
+    }
     s->d_prec = diag;
     return MK_OK;
 }
@@ -360,6 +372,8 @@ __global__ __launch_bounds__(MK_BLOCK) void mk_fill_kernel(double *v, int64_t n,
 static void mk_drop_precon_ilu(mk_solver *s) {
     if (s->precon_ilu) mk_ilu_release(s->precon_ilu);
     s->precon_ilu = nullptr;
+    if (s->precon_lbfgs) mk_lbfgs_release(s->precon_lbfgs);   // (an L-BFGS operator goes wherever a factorization goes)
+    s->precon_lbfgs = nullptr;
 }
 
 extern "C" int mk_solver_set_precon_callback(mk_solver *s, mk_precon_fn fn, void *user) {
@@ -453,6 +467,38 @@ extern "C" int mk_solver_set_precon_ilu(mk_solver *s, const mk_ilu *F) {
     if (s->precon_op) mk_release_operand(s->precon_op);
     s->precon_op = nullptr;
     s->precon_ilu = F;
+    s->precon_fn = mk_precon_on_device;                      // (marks "general preconditioner" at the call sites)
+    s->precon_user = nullptr;
+    s->d_prec = s->d_ones;
+    return MK_OK;
+}
+
+extern "C" int mk_solver_set_precon_lbfgs(mk_solver *s, const mk_lbfgs *F) {
+    MK_ARG(s);
+    if (!F) {
+        mk_drop_precon_ilu(s);
+        s->precon_fn = nullptr;
+        s->d_prec = nullptr;
+        return MK_OK;
+    }
+    if (!s->takes_precon()) return mk_fail(MK_ERR_UNSUPPORTED, "this solver kind has no preconditioner hook");
+    if (s->A->ex.mode >= 0)
+        return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_set_precon_lbfgs: L-BFGS operators are single-GPU (the solver's "
+                       "operator carries an exchange plan)");
+    if (mk_lbfgs_rows(F) != s->n)
+        return mk_fail(MK_ERR_ARG, "mk_solver_set_precon_lbfgs: the operator has %lld rows, the solver %lld",
+                       (long long)mk_lbfgs_rows(F), (long long)s->n);
+    const size_t len = (size_t)(s->n > 0 ? s->n : 1);
+    if (!s->d_ones) {
+        MK_HIP(hipMalloc((void **)&s->d_ones, sizeof(double) * len + 16));
+        hipLaunchKernelGGL(mk_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, s->stream, s->d_ones, (int64_t)len, 1.0);
+        MK_HIP(hipGetLastError());
+    }
+    mk_lbfgs_hold(F);                                        // take the new reference first, then drop the old ones
+    mk_drop_precon_ilu(s);
+    if (s->precon_op) mk_release_operand(s->precon_op);
+    s->precon_op = nullptr;
+    s->precon_lbfgs = F;
     s->precon_fn = mk_precon_on_device;                      // (marks "general preconditioner" at the call sites)
     s->precon_user = nullptr;
     s->d_prec = s->d_ones;

@@ -104,6 +104,17 @@ class KrylovMethod(object):
                 raise ValueError('%s: precon has shape %s, expected %s'
                                  % (self.__class__.__name__, precon.shape, (self.op.shape[0], self.op.shape[0])))
             return precon
+        # * an inverse L-BFGS operator (`lbfgs.InverseLBFGSOperator`) is applied ON the device by its two-loop recursion;
+        #   the forward classes are not preconditioners and stay on the host-callback route below
+        from .lbfgs import InverseLBFGSOperator
+        if isinstance(precon, InverseLBFGSOperator) and precon._is_inverse:
+            if getattr(self.op, 'local_size', None) is not None:
+                raise NotImplementedError('%s: L-BFGS operators are single-GPU; the operator is row-partitioned'
+                                          % self.__class__.__name__)
+            if precon.shape != (self.op.shape[0], self.op.shape[0]):
+                raise ValueError('%s: precon has shape %s, expected %s'
+                                 % (self.__class__.__name__, precon.shape, (self.op.shape[0], self.op.shape[0])))
+            return precon
         # * a device matrix (CsrOperator -- e.g. the inverted diagonal blocks of `tools.block_jacobi`) or a block
         #   operator of device matrices is applied ON the device, as a product at the same sites
         from .linop import CsrOperator
@@ -208,6 +219,16 @@ class DeviceRun(object):
             self.ilu_precon, precon_diag = precon_diag, None
             try:
                 _lib.check(self.lib.mk_solver_set_precon_ilu(self.handle, self.ilu_precon._live()))
+            except Exception:
+                self.lib.mk_solver_destroy(self.handle)
+                self.handle = ctypes.c_void_p()
+                raise
+        self.lbfgs_precon = None
+        from .lbfgs import InverseLBFGSOperator
+        if isinstance(precon_diag, InverseLBFGSOperator) and precon_diag._is_inverse:
+            self.lbfgs_precon, precon_diag = precon_diag, None
+            try:
+                _lib.check(self.lib.mk_solver_set_precon_lbfgs(self.handle, self.lbfgs_precon._live()))
             except Exception:
                 self.lib.mk_solver_destroy(self.handle)
                 self.handle = ctypes.c_void_p()
@@ -318,6 +339,8 @@ class DeviceRun(object):
             _lib.check(self.lib.mk_solver_set_precon_csr(handle, self.device_precon.dev.handle))
         if self.ilu_precon is not None:
             _lib.check(self.lib.mk_solver_set_precon_ilu(handle, self.ilu_precon._live()))
+        if self.lbfgs_precon is not None:
+            _lib.check(self.lib.mk_solver_set_precon_lbfgs(handle, self.lbfgs_precon._live()))
         if self.d_prec is not None:
             _lib.check(self.lib.mk_solver_set_precon_diag(handle, self.d_prec.ptr))
 
