@@ -484,7 +484,7 @@ struct CgSolver : mk_solver {
         const MkPlan *plan = A ? mk_csr_plan(A) : nullptr;
         // one device, or one rank's slab under a halo exchange (the march takes the neighbours' planes from the received entries)
         const bool slab = plan && A->ex.mode == 0 && nx == n + A->ex.n_halo && (plan->pen_xlo >= 0 || plan->pen_xhi >= 0);
-        fused = want_fuse() && plan && mk_fmt_march(plan->fmt) && !precon_fn && A->nops == 0 && !A->comp_kind &&
+        fused = want_fuse() && plan && mk_fmt_march(plan->fmt) && !general_precon() && A->nops == 0 && !A->comp_kind &&
                 ((!mk_comm_active() && A->ex.mode < 0 && nx == n) || slab);
         flushed = false;
         x_applied = 0;
@@ -525,7 +525,7 @@ struct CgSolver : mk_solver {
         }
         if (d_prec) {
             mk_launch_stream(this, MkOpMul{d_prec, d_r, d_Ap}, n);          // y = precon * r    cg.py:91-92
-            if (precon_fn && host_precon(d_r, d_Ap) != MK_OK) return MK_ERR_STATE;
+            if (general_precon() && apply_precon(d_r, d_Ap) != MK_OK) return MK_ERR_STATE;
             mk_launch_stream(this, MkOpDot<1>{d_r, d_Ap}, n);               // ry = <r, y>       cg.py:99
         } else {
             mk_launch_stream(this, MkOpDot<1>{d_r, d_r}, n);                // ry = <r, r>       cg.py:99
@@ -603,8 +603,8 @@ struct CgSolver : mk_solver {
         if ((rc = allreduce(0, 1)) != MK_OK) return rc;
         mk_launch_stream(this, CgUpdateR{d_part, np_spmv, d_scal, d_status, par, prm.check_curvature, d_Ap, d_r,
                                          d_prec, 0.0, false}, n);
-        if (precon_fn) {                                    // y = precon * r ; <r, y> re-formed   cg.py:137-138,146
-            if ((rc = host_precon(d_r, d_Ap)) != MK_OK) return rc;
+        if (general_precon()) {                             // y = precon * r ; <r, y> re-formed   cg.py:137-138,146
+            if ((rc = apply_precon(d_r, d_Ap)) != MK_OK) return rc;
             mk_launch_stream(this, MkOpDot<1>{d_r, d_Ap}, n);
         }
         if ((rc = allreduce(1, 1)) != MK_OK) return rc;

@@ -243,7 +243,7 @@ struct CgsSolver : mk_solver {
         mk_launch_stream(this, MkOpCopy{d_r0, d_u}, n);                        // u = r0           cgs.py:73
         mk_launch_stream(this, MkOpCopy{d_r0, d_p}, n);                        // p = r0.copy()    cgs.py:74
         if (d_prec) mk_launch_stream(this, MkOpMul{d_prec, d_r0, d_y}, n);     // y = precon * p   cgs.py:79-80
-        if (precon_fn && (rc = host_precon(d_p, d_y)) != MK_OK) return rc;
+        if (general_precon() && (rc = apply_precon(d_p, d_y)) != MK_OK) return rc;
         return MK_OK;
     }
 
@@ -258,13 +258,13 @@ struct CgsSolver : mk_solver {
         const int par = (int)(it & 1);
         double *yin = d_prec ? d_y : d_p;
         int rc;
-        if (precon_fn && it > 0 && (rc = host_precon(d_p, d_y)) != MK_OK) return rc;   // y = precon * p   cgs.py:79-80
+        if (general_precon() && it > 0 && (rc = apply_precon(d_p, d_y)) != MK_OK) return rc;   // y = precon * p   cgs.py:79-80
         if ((rc = exchange(yin)) != MK_OK) return rc;
         mk_launch_spmv(this, yin, BEpi{d_r0, d_v, mk_store_nt(A)}, true, CountGate{d_status, 2 * it});
         if ((rc = allreduce(SLOT_SIGMA, 1)) != MK_OK) return rc;
-        mk_launch_stream(this, OpC{d_part, np_spmv, d_scal, par, d_u, d_v, d_q, d_z, d_x, d_prec, 0.0, precon_fn ? 1 : 0}, n);
-        if (precon_fn) {                                    // z = precon * (u + q) ; x += alpha z     cgs.py:88-94
-            if ((rc = host_precon(d_z, d_z)) != MK_OK) return rc;
+        mk_launch_stream(this, OpC{d_part, np_spmv, d_scal, par, d_u, d_v, d_q, d_z, d_x, d_prec, 0.0, general_precon() ? 1 : 0}, n);
+        if (general_precon()) {                             // z = precon * (u + q) ; x += alpha z     cgs.py:88-94
+            if ((rc = apply_precon(d_z, d_z)) != MK_OK) return rc;
             mk_launch_stream(this, OpXZ{d_scal, d_z, d_x, 0.0}, n);
         }
         if ((rc = exchange(d_z)) != MK_OK) return rc;

@@ -36,10 +36,10 @@ struct MkIluSweep {    // one sweep's row lists: rows of level L are rows[lev[L]
     std::vector<MkIluLaunch> plan;
 };
 
-struct mk_ilu {
+struct mk_ilu : MkDeviceOp {
     const mk_csr *A = nullptr;     // borrowed pattern (A->dependents counts this factor)
     int kind = 0;                  // 0 ILU(0), 1 IC(0)
-    int64_t n = 0, nnz = 0;
+    int64_t nnz = 0;
     double *d_val = nullptr;       // factor values on A's pattern (nnz + MK_CSR_PAD)
     int32_t *d_diag = nullptr;     // position of the diagonal entry of each row
     MkIluSweep fw, bw;
@@ -48,8 +48,8 @@ struct mk_ilu {
     int *d_status = nullptr;       // smallest failing row of the factorization (INT_MAX: none)
     double analysis_us = 0.0, factor_us = 0.0;
     size_t bytes = 0;              // device bytes owned by the factor
-    mutable int users = 0;         // solvers holding the factor (mk_solver_set_precon_ilu)
-    mutable bool doomed = false;   // mk_ilu_destroy was called while solvers still held it
+    ~mk_ilu() override;
+    int enqueue(const double *in, double *out, hipStream_t stream, int *flags, int64_t *q) const override;
 };
 
 struct MkIluView {                 // what a kernel reads of a factor and one sweep
@@ -180,38 +180,26 @@ static void mk_ilu_sweep(const mk_ilu *F, const MkIluSweep &S, const double *in,
 }
 
 // out = M^-1 in (in == out allowed).  Used by mk_ilu_apply and by the solver's preconditioner sites (mk_solver.hip).
-int mk_ilu_enqueue(const mk_ilu *F, const double *in, double *out, hipStream_t st, int *flags, int64_t *q) {
-    if (F->n == 0) return MK_OK;
-    if (F->kind == 0) mk_ilu_sweep<MK_ILU_FWD>(F, F->fw, in, out, st, flags, q);
-    else mk_ilu_sweep<MK_ILU_FWD_DIV>(F, F->fw, in, out, st, flags, q);
-    mk_ilu_sweep<MK_ILU_BWD>(F, F->bw, out, out, st, flags, q);
+int mk_ilu::enqueue(const double *in, double *out, hipStream_t st, int *flags, int64_t *q) const {
+    if (n == 0) return MK_OK;
+    if (kind == 0) mk_ilu_sweep<MK_ILU_FWD>(this, fw, in, out, st, flags, q);
+    else mk_ilu_sweep<MK_ILU_FWD_DIV>(this, fw, in, out, st, flags, q);
+    mk_ilu_sweep<MK_ILU_BWD>(this, bw, out, out, st, flags, q);
     MK_HIP(hipGetLastError());
     return MK_OK;
 }
 
-int64_t mk_ilu_rows(const mk_ilu *F) { return F->n; }
-
-static void mk_ilu_free(mk_ilu *F) {
+mk_ilu::~mk_ilu() {
     if (mk_ctx().ready) hipStreamSynchronize(mk_ctx().stream);
-    hipFree(F->d_val);
-    hipFree(F->d_diag);
-    hipFree(F->fw.d_rows);
-    hipFree(F->fw.d_lev);
-    hipFree(F->bw.d_rows);
-    hipFree(F->bw.d_lev);
-    hipFree(F->d_nohalt);
-    hipFree(F->d_status);
-    const mk_csr *A = F->A;
-    delete F;
+    hipFree(d_val);
+    hipFree(d_diag);
+    hipFree(fw.d_rows);
+    hipFree(fw.d_lev);
+    hipFree(bw.d_rows);
+    hipFree(bw.d_lev);
+    hipFree(d_nohalt);
+    hipFree(d_status);
     if (A) mk_release_operand(A);
-}
-
-void mk_ilu_hold(const mk_ilu *F) { F->users += 1; }
-
-void mk_ilu_release(const mk_ilu *F) {
-    if (!F) return;
-    F->users -= 1;
-    if (F->users <= 0 && F->doomed) mk_ilu_free(const_cast<mk_ilu *>(F));
 }
 
 // ------------------------------------------------------------------ host analysis
@@ -349,7 +337,7 @@ static int mk_ilu_create(const mk_csr *A, int kind, mk_ilu **out) {
     int rc = MK_OK;
     const auto fail = [&](int code) {
         hipFree(d_tmap);
-        mk_ilu_free(F);
+        delete F;
         return code;
     };
     if ((rc = mk_ilu_upload(&F->d_diag, dg, &F->bytes)) != MK_OK || (rc = mk_ilu_upload(&F->fw.d_rows, rows_f, &F->bytes)) != MK_OK ||
@@ -383,7 +371,7 @@ static int mk_ilu_create(const mk_csr *A, int kind, mk_ilu **out) {
     hipFree(d_tmap);
     d_tmap = nullptr;
     if (bad != INT_MAX) {
-        mk_ilu_free(F);
+        delete F;
         return kind ? mk_fail(MK_ERR_STATE, "%s: breakdown in row %d (the pivot is not positive)", fn, bad)
                     : mk_fail(MK_ERR_STATE, "%s: zero pivot in row %d", fn, bad);
     }
@@ -399,20 +387,19 @@ extern "C" int mk_ilu0_create(const mk_csr *A, mk_ilu **out) { return mk_ilu_cre
 extern "C" int mk_ic0_create(const mk_csr *A, mk_ilu **out) { return mk_ilu_create(A, 1, out); }
 
 extern "C" int mk_ilu_destroy(mk_ilu *F) {
-    if (!F) return MK_OK;
-    if (F->users > 0) {                                          // solvers still apply it: freed with the last of them
-        F->doomed = true;
-        return MK_OK;
-    }
-    mk_ilu_free(F);
+    if (F) F->destroy();                                         // (while solvers still apply it: freed with the last of them)
     return MK_OK;
+}
+
+extern "C" int mk_solver_set_precon_ilu(mk_solver *s, const mk_ilu *F) {
+    return mk_set_precon_object(s, F, "mk_solver_set_precon_ilu", "factor", "incomplete factorizations");
 }
 
 extern "C" int mk_ilu_apply(const mk_ilu *F, const double *in_dev, double *out_dev) {
     MK_REQUIRE_INIT();
     MK_ARG(F && (F->n == 0 || (in_dev && out_dev)));
     MK_ARG(MK_ALIGNED16(in_dev) && MK_ALIGNED16(out_dev));
-    return mk_ilu_enqueue(F, in_dev, out_dev, mk_ctx().stream, nullptr, nullptr);
+    return F->enqueue(in_dev, out_dev, mk_ctx().stream, nullptr, nullptr);
 }
 
 extern "C" int mk_ilu_info(const mk_ilu *F, int64_t *info, int32_t cap) {

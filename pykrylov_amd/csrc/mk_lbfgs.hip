@@ -22,8 +22,8 @@
 constexpr int MK_LBFGS_GROUP = 8;                     // columns of one multi-dot launch (their accumulators stay in registers)
 constexpr int MK_LBFGS_SLOTS = 2 + MK_LBFGS_GROUP;    // partial-sum slots: 0 / 1 the apply chain, 2 .. the multi-dot
 
-struct mk_lbfgs {
-    int64_t n = 0, ld = 0;
+struct mk_lbfgs : MkDeviceOp {
+    int64_t ld = 0;
     int npairs = 0, scaling = 0;
     double *d_S = nullptr, *d_Y = nullptr;     // the rings: npairs columns of ld doubles each
     double *d_sc = nullptr;                    // ys[npairs], alpha[npairs], gamma
@@ -39,8 +39,8 @@ struct mk_lbfgs {
     int64_t stores = 0, rejected = 0;
     size_t bytes = 0;
     mutable int64_t last_launches = 0, applies = 0;
-    mutable int users = 0;                     // solvers holding the operator (mk_solver_set_precon_lbfgs)
-    mutable bool doomed = false;               // mk_lbfgs_destroy was called while solvers still held it
+    ~mk_lbfgs() override;
+    int enqueue(const double *in, double *out, hipStream_t stream, int *flags, int64_t *q) const override;
     const double *S(int k) const { return d_S + (size_t)k * (size_t)ld; }
     const double *Y(int k) const { return d_Y + (size_t)k * (size_t)ld; }
     int oldest(int i) const { return ((insert - count + i) % npairs + npairs) % npairs; }   // i-th stored pair, oldest first
@@ -159,7 +159,8 @@ static void mk_lbfgs_launch(const mk_lbfgs *F, int j, int kprev, const double *u
 // out = H in by the two-loop recursion (in == out allowed): 2p + 1 launches for p stored pairs; with none a copy, or nothing
 // when in == out.  `q` = the solver's kernel counter (each launch takes the halt word flags[(*q)++ & 1]), or null for a
 // standalone run (d_nohalt).  Used by mk_lbfgs_apply and by the solver's preconditioner sites (mk_solver.hip).
-int mk_lbfgs_enqueue(const mk_lbfgs *F, const double *in, double *out, hipStream_t st, int *flags, int64_t *q) {
+int mk_lbfgs::enqueue(const double *in, double *out, hipStream_t st, int *flags, int64_t *q) const {
+    const mk_lbfgs *F = this;
     const auto halt = [&] { return q ? MkHalt{flags, (int)((*q)++ & 1), 0} : MkHalt{F->d_nohalt, 0, 0}; };
     const int p = F->count;
     F->applies += 1;
@@ -198,8 +199,6 @@ int mk_lbfgs_enqueue(const mk_lbfgs *F, const double *in, double *out, hipStream
     MK_HIP(hipGetLastError());
     return MK_OK;
 }
-
-int64_t mk_lbfgs_rows(const mk_lbfgs *F) { return F->n; }
 
 // ------------------------------------------------------------------ multi-dot
 struct MkMultiDot {
@@ -358,24 +357,15 @@ __global__ void mk_lbfgs_set_kernel(double *sc, int k, double ys, int kg, double
 }
 
 // ------------------------------------------------------------------ lifetime
-static void mk_lbfgs_free(mk_lbfgs *F) {
+mk_lbfgs::~mk_lbfgs() {
     if (mk_ctx().ready) hipStreamSynchronize(mk_ctx().stream);
-    hipFree(F->d_S);
-    hipFree(F->d_Y);
-    hipFree(F->d_sc);
-    hipFree(F->d_part);
-    hipFree(F->d_res);
-    hipFree(F->d_coef);
-    hipFree(F->d_nohalt);
-    delete F;
-}
-
-void mk_lbfgs_hold(const mk_lbfgs *F) { F->users += 1; }
-
-void mk_lbfgs_release(const mk_lbfgs *F) {
-    if (!F) return;
-    F->users -= 1;
-    if (F->users <= 0 && F->doomed) mk_lbfgs_free(const_cast<mk_lbfgs *>(F));
+    hipFree(d_S);
+    hipFree(d_Y);
+    hipFree(d_sc);
+    hipFree(d_part);
+    hipFree(d_res);
+    hipFree(d_coef);
+    hipFree(d_nohalt);
 }
 
 // ======================================================================================
@@ -405,7 +395,7 @@ extern "C" int mk_lbfgs_create(int64_t n, int32_t npairs, int32_t scaling, mk_lb
         hipMalloc((void **)&F->d_res, nres) != hipSuccess || hipMalloc((void **)&F->d_coef, nres) != hipSuccess ||
         hipMalloc((void **)&F->d_nohalt, 2 * sizeof(int)) != hipSuccess) {
         (void)hipGetLastError();
-        mk_lbfgs_free(F);
+        delete F;
         return mk_fail(MK_ERR_HIP, "mk_lbfgs_create: out of device memory for 2 x %d columns of %lld doubles", (int)npairs,
                        (long long)n);
     }
@@ -422,13 +412,12 @@ extern "C" int mk_lbfgs_create(int64_t n, int32_t npairs, int32_t scaling, mk_lb
 }
 
 extern "C" int mk_lbfgs_destroy(mk_lbfgs *F) {
-    if (!F) return MK_OK;
-    if (F->users > 0) {                                          // solvers still apply it: freed with the last of them
-        F->doomed = true;
-        return MK_OK;
-    }
-    mk_lbfgs_free(F);
+    if (F) F->destroy();                                         // (while solvers still apply it: freed with the last of them)
     return MK_OK;
+}
+
+extern "C" int mk_solver_set_precon_lbfgs(mk_solver *s, const mk_lbfgs *F) {
+    return mk_set_precon_object(s, F, "mk_solver_set_precon_lbfgs", "operator", "L-BFGS operators");
 }
 
 extern "C" int mk_lbfgs_store(mk_lbfgs *F, const double *s_dev, const double *y_dev, double threshold, int32_t *accepted) {
@@ -497,7 +486,7 @@ extern "C" int mk_lbfgs_apply(const mk_lbfgs *F, const double *in_dev, double *o
     MK_REQUIRE_INIT();
     MK_ARG(F && in_dev && out_dev);
     MK_ARG(MK_ALIGNED16(in_dev) && MK_ALIGNED16(out_dev));
-    return mk_lbfgs_enqueue(F, in_dev, out_dev, mk_ctx().stream, nullptr, nullptr);
+    return F->enqueue(in_dev, out_dev, mk_ctx().stream, nullptr, nullptr);
 }
 
 extern "C" int mk_lbfgs_forward_dots(const mk_lbfgs *F, const double *in_dev, int32_t use_gamma, double *a_host) {

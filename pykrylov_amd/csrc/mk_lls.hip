@@ -993,7 +993,7 @@ struct LlsSolver : mk_solver {
     int64_t itnlim = 0;
     // M / N as host callbacks (mk_solver_set_lls_precon_callback): the kernels run with a diagonal of ones and the
     // vector `u = M(Mu)` / `v = N(Nv)` is replaced by the callback's result right after the kernel that formed it;
-    // <u, Mu> / <v, Nv> are then re-formed by a dot kernel (same scheme as mk_solver::host_precon)
+    // <u, Mu> / <v, Nv> are then re-formed by a dot kernel (same scheme as mk_solver::apply_precon)
     mk_precon_fn fn_m = nullptr, fn_n = nullptr;
     void *user_m = nullptr, *user_n = nullptr;
     double *d_ones_m = nullptr, *d_ones_n = nullptr, *h_cb_in = nullptr, *h_cb_out = nullptr;

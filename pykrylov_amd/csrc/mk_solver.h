@@ -30,41 +30,63 @@ int mk_comm_allgather(const double *mine_dev, double *full_dev, int64_t count_pe
 int mk_exchange_begin(const mk_csr *A, double *x_ext);     // may leave the messages in flight on a second stream
 int mk_exchange_wait(const mk_csr *A, hipStream_t stream); // ... until here
 
-// Incomplete factorizations (mk_ilu.hip): out = M^-1 in on `stream` (in == out allowed); every launch takes the halt word
-// flags[(*q)++ & 1] (q null: never halted).  A solver holds a factor with mk_ilu_hold and lets go with mk_ilu_release.
-int mk_ilu_enqueue(const mk_ilu *F, const double *in, double *out, hipStream_t stream, int *flags, int64_t *q);
-int64_t mk_ilu_rows(const mk_ilu *F);
-void mk_ilu_hold(const mk_ilu *F);
-void mk_ilu_release(const mk_ilu *F);
+// A device object that applies out = P in under the loop's halt words: the incomplete factorizations (mk_ilu.hip) and the
+// inverse L-BFGS operator (mk_lbfgs.hip).  A solver that applies it holds it; destroying it meanwhile is deferred to the
+// last release.  The destructor of the derived object frees its device memory.
+struct MkDeviceOp {
+    int64_t n = 0;                 // rows
+    mutable int users = 0;         // solvers holding the object
+    mutable bool doomed = false;   // `destroy` was called while solvers still held it
+    virtual ~MkDeviceOp() = default;
+    // out = P in on `stream` (in == out allowed); every launch takes the halt word flags[(*q)++ & 1] (q null: a standalone
+    // run, never halted)
+    virtual int enqueue(const double *in, double *out, hipStream_t stream, int *flags, int64_t *q) const = 0;
+    void hold() const { users += 1; }
+    void release() const {
+        if (--users <= 0 && doomed) delete this;
+    }
+    void destroy() {               // (the mk_*_destroy entry points)
+        if (users > 0) doomed = true;
+        else delete this;
+    }
+};
 
-// Inverse L-BFGS operator (mk_lbfgs.hip): out = H in on `stream` by the two-loop recursion (in == out allowed), the same
-// halt-word protocol and hold / release as the factorizations above.
-int mk_lbfgs_enqueue(const mk_lbfgs *F, const double *in, double *out, hipStream_t stream, int *flags, int64_t *q);
-int64_t mk_lbfgs_rows(const mk_lbfgs *F);
-void mk_lbfgs_hold(const mk_lbfgs *F);
-void mk_lbfgs_release(const mk_lbfgs *F);
+// The one preconditioner a solver carries.  A diagonal is multiplied inside the loop's kernels (mk_solver::d_prec).  With
+// one of the general kinds the kernels run with a diagonal of ones (`1.0 * v` is exact) and every preconditioned vector is
+// replaced by `apply_precon`'s result right after the kernel that produced it; inner products with it are re-formed by a
+// separate dot kernel.
+enum MkPreconKind {
+    MK_PRECON_NONE = 0,
+    MK_PRECON_DIAG,        // mk_solver_set_precon_diag: the borrowed diagonal is d_prec itself
+    MK_PRECON_HOST,        // mk_solver_set_precon_callback: `fn(user, in, out)` on the host, through pinned buffers
+    MK_PRECON_CSR,         // mk_solver_set_precon_csr: a device matrix or composite `op` (counted in op->dependents), e.g. the
+                           // inverted diagonal blocks of block-Jacobi; the product stays in HBM
+    MK_PRECON_OBJECT       // mk_solver_set_precon_ilu / _lbfgs: a held MkDeviceOp `obj`, applied in place
+};
+
+struct MkPrecon {
+    MkPreconKind kind = MK_PRECON_NONE;
+    mk_precon_fn fn = nullptr;
+    void *user = nullptr;
+    const mk_csr *op = nullptr;
+    const MkDeviceOp *obj = nullptr;
+};
 
 struct mk_solver {
     const mk_csr *A = nullptr;
     const mk_csr *At = nullptr;     // transposed matrix (least-squares solvers only)
-    const double *d_prec = nullptr; // diagonal of a Jacobi-type preconditioner M^-1 (borrowed, n entries) or null
-    // general preconditioner through a host callback (mk_solver_set_precon_callback): the kernels run with a
-    // diagonal of ones (`1.0 * v` is exact) and every preconditioned vector is replaced by the callback's result
-    // right after the kernel that produced it; inner products with it are re-formed by a separate dot kernel
-    mk_precon_fn precon_fn = nullptr;
-    void *precon_user = nullptr;
-    double *d_ones = nullptr, *h_pin = nullptr, *h_pout = nullptr;
-    // ... or through a DEVICE operator (mk_solver_set_precon_csr: a sparse approximate inverse, e.g. the inverted
-    // diagonal blocks of block-Jacobi, as a device matrix or composite): the same sites, the product stays in HBM
-    const mk_csr *precon_op = nullptr;
-    double *d_ptmp = nullptr;       // product target when a site preconditions a vector in place
-    // ... or through an incomplete factorization (mk_solver_set_precon_ilu: ILU(0) / IC(0)): two level-scheduled triangular
-    // sweeps on the device at the same sites, in place
-    const mk_ilu *precon_ilu = nullptr;
-    // ... or through an inverse L-BFGS operator (mk_solver_set_precon_lbfgs): the two-loop recursion at the same sites
-    const mk_lbfgs *precon_lbfgs = nullptr;
-    int *d_nohalt = nullptr;        // two zero words: the halt input of a product that must run after the loop has ended
-    int host_precon(const double *in_dev, double *out_dev, bool force = false);   // out = precon * in ; unless `force`, a no-op once the loop has halted
+    MkPrecon precon;
+    const double *d_prec = nullptr; // what the kernels multiply by: the diagonal (n entries), d_ones for a general kind, or null
+    double *d_ones = nullptr;       // (owned, allocated with the first general preconditioner)
+    double *h_pin = nullptr, *h_pout = nullptr;   // pinned staging of the host callback
+    double *d_ptmp = nullptr;       // product target when a site preconditions a vector in place by a device matrix
+    int *d_nohalt = nullptr;        // two zero words: the halt input of a kernel that must run after the loop has ended
+    bool general_precon() const { return precon.kind >= MK_PRECON_HOST; }
+    // `next` (a general kind) replaces whatever is attached; the messages name the entry point `who`, and for an object what
+    // it is (`noun`, `plural`)
+    int attach_precon(const MkPrecon &next, const char *who, const char *noun = nullptr, const char *plural = nullptr);
+    void clear_precon();            // back to MK_PRECON_NONE: the only place a preconditioner's reference is released
+    int apply_precon(const double *in_dev, double *out_dev, bool force = false);   // out = precon * in ; unless `force`, a no-op once the loop has halted
     mk_params prm{};
     int64_t n = 0;        // local rows = length of every solver vector
     int64_t nx = 0;       // length of vectors that feed an SpMV (n + halo)
@@ -129,6 +151,9 @@ struct mk_solver {
     void spmv_end();
     int collect_spmv_timing();
 };
+
+// attach a device object as `s`'s preconditioner (F null: none); `who`, `noun`, `plural` as in mk_solver::attach_precon
+int mk_set_precon_object(mk_solver *s, const MkDeviceOp *F, const char *who, const char *noun, const char *plural);
 
 mk_solver *mk_make_cg();
 mk_solver *mk_make_bicgstab();

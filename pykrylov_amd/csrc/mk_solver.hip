@@ -18,6 +18,8 @@ int mk_solver::init_common(const mk_csr *A_, const mk_params *p) {
     MK_HIP(hipMalloc((void **)&d_scal, sizeof(double) * MK_NSCAL));
     MK_HIP(hipMalloc((void **)&d_part, sizeof(double) * MK_NDOT * MK_MAXP));
     MK_HIP(hipMalloc((void **)&d_halt, 2 * sizeof(int)));
+    MK_HIP(hipMalloc((void **)&d_nohalt, 2 * sizeof(int)));
+    MK_HIP(hipMemsetAsync(d_nohalt, 0, 2 * sizeof(int), stream));
     MK_HIP(hipMalloc((void **)&d_status, sizeof(MkStatus)));
     MK_HIP(hipMalloc((void **)&d_hist, sizeof(double) * 2 * MK_HIST_RING));
     MK_HIP(hipHostMalloc((void **)&h_status, sizeof(MkStatus), hipHostMallocDefault));
@@ -33,58 +35,59 @@ int mk_solver::init_common(const mk_csr *A_, const mk_params *p) {
     return MK_OK;
 }
 
-// (stands in for the callback when the preconditioner is a device operator: every `if (precon_fn ...)` site stays as it is)
-static int mk_precon_on_device(void *, const double *, double *) { return 1; }
-
-int mk_solver::host_precon(const double *in_dev, double *out_dev, bool force) {
-    if (!precon_fn) return MK_OK;
-    if (precon_ilu) {
-        // out = M^-1 in by the factor's sweeps; each launch obeys the halt words like the product below
-        const int rc = force ? mk_ilu_enqueue(precon_ilu, in_dev, out_dev, stream, nullptr, nullptr)
-                             : mk_ilu_enqueue(precon_ilu, in_dev, out_dev, stream, d_halt, &q);
-        return rc != MK_OK ? rc : mk_ctx().pending_rc;
-    }
-    if (precon_lbfgs) {
-        // out = H in by the chain of the two-loop recursion, under the same halt words
-        const int rc = force ? mk_lbfgs_enqueue(precon_lbfgs, in_dev, out_dev, stream, nullptr, nullptr)
-                             : mk_lbfgs_enqueue(precon_lbfgs, in_dev, out_dev, stream, d_halt, &q);
-        return rc != MK_OK ? rc : mk_ctx().pending_rc;
-    }
-    if (precon_op) {
-        // out = precon_op * in on the device.  Like every kernel of the loop the product obeys the halt words: once the
-        // loop condition has failed it is a no-op, exactly when the reference applies nothing more -- unless `force`.
-        double *dst = (in_dev == out_dev) ? d_ptmp : out_dev;
-        const int grid = mk_grid_spmv_for(precon_op);
-        if (force) {
-            mk_spmv_launch_blocks(precon_op, grid, stream, in_dev, MkPlainEpi{dst}, MkNoGate(),
-                                  [&] { return MkHalt{d_nohalt, 0, 0}; }, d_part);
-            if (dst != out_dev) MK_HIP(hipMemcpyAsync(out_dev, dst, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-        } else {
-            mk_spmv_launch_blocks(precon_op, grid, stream, in_dev, MkPlainEpi{dst}, MkNoGate(),
-                                  [&] { return next_halt(); }, d_part);
-            if (dst != out_dev) mk_launch_stream(this, MkOpCopy{dst, out_dev}, n);
+int mk_solver::apply_precon(const double *in_dev, double *out_dev, bool force) {
+    switch (precon.kind) {
+        case MK_PRECON_OBJECT: {
+            // out = P in by the object's own launches (the factor's sweeps, the chain of the two-loop recursion); each obeys
+            // the halt words like the product below
+            const int rc = force ? precon.obj->enqueue(in_dev, out_dev, stream, nullptr, nullptr)
+                                 : precon.obj->enqueue(in_dev, out_dev, stream, d_halt, &q);
+            return rc != MK_OK ? rc : mk_ctx().pending_rc;
         }
-        return mk_ctx().pending_rc;
+        case MK_PRECON_CSR: {
+            // out = op * in on the device.  Like every kernel of the loop the product obeys the halt words: once the loop
+            // condition has failed it is a no-op, exactly when the reference applies nothing more -- unless `force`.
+            double *dst = (in_dev == out_dev) ? d_ptmp : out_dev;
+            const int grid = mk_grid_spmv_for(precon.op);
+            if (force) {
+                mk_spmv_launch_blocks(precon.op, grid, stream, in_dev, MkPlainEpi{dst}, MkNoGate(),
+                                      [&] { return MkHalt{d_nohalt, 0, 0}; }, d_part);
+                if (dst != out_dev) MK_HIP(hipMemcpyAsync(out_dev, dst, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+            } else {
+                mk_spmv_launch_blocks(precon.op, grid, stream, in_dev, MkPlainEpi{dst}, MkNoGate(),
+                                      [&] { return next_halt(); }, d_part);
+                if (dst != out_dev) mk_launch_stream(this, MkOpCopy{dst, out_dev}, n);
+            }
+            return mk_ctx().pending_rc;
+        }
+        case MK_PRECON_HOST: {
+            int h = 0;
+            MK_HIP(hipMemcpyAsync(&h, d_halt + (q & 1), sizeof(int), hipMemcpyDeviceToHost, stream));   // the next kernel's word
+            if (n > 0) MK_HIP(hipMemcpyAsync(h_pin, in_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, stream));
+            MK_HIP(hipStreamSynchronize(stream));
+            if (h && !force) return MK_OK;                   // the loop has ended: the reference applies nothing more
+            if (precon.fn(precon.user, h_pin, h_pout) != 0) {
+                const int rc = mk_fail(MK_ERR_STATE, "the host preconditioner callback reported a failure");
+                if (mk_ctx().pending_rc == MK_OK) mk_ctx().pending_rc = rc;
+                return rc;
+            }
+            if (n > 0) MK_HIP(hipMemcpyAsync(out_dev, h_pout, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream));
+            return MK_OK;
+        }
+        default: return MK_OK;                               // (a diagonal acts inside the kernels)
     }
-    int h = 0;
-    MK_HIP(hipMemcpyAsync(&h, d_halt + (q & 1), sizeof(int), hipMemcpyDeviceToHost, stream));   // the next kernel's word
-    if (n > 0) MK_HIP(hipMemcpyAsync(h_pin, in_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, stream));
-    MK_HIP(hipStreamSynchronize(stream));
-    if (h && !force) return MK_OK;                           // the loop has ended: the reference applies nothing more
-    if (precon_fn(precon_user, h_pin, h_pout) != 0) {
-        const int rc = mk_fail(MK_ERR_STATE, "the host preconditioner callback reported a failure");
-        if (mk_ctx().pending_rc == MK_OK) mk_ctx().pending_rc = rc;
-        return rc;
-    }
-    if (n > 0) MK_HIP(hipMemcpyAsync(out_dev, h_pout, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream));
-    return MK_OK;
+}
+
+void mk_solver::clear_precon() {
+    if (precon.kind == MK_PRECON_CSR) mk_release_operand(precon.op);
+    if (precon.kind == MK_PRECON_OBJECT) precon.obj->release();
+    precon = MkPrecon{};
+    d_prec = nullptr;
 }
 
 mk_solver::~mk_solver() {
     if (mk_ctx().ready) hipStreamSynchronize(mk_ctx().stream);
-    if (precon_op) mk_release_operand(precon_op);
-    if (precon_ilu) mk_ilu_release(precon_ilu);
-    if (precon_lbfgs) mk_lbfgs_release(precon_lbfgs);
+    clear_precon();
     if (At) mk_release_operand(At);
     if (A && counted_user) mk_csr_count_users(A, -1);
     if (A) mk_release_operand(A);
@@ -346,21 +349,14 @@ extern "C" int mk_csr_set_row_block(mk_csr *A, int on) {
     return MK_OK;
 }
 
+// Every setter below REPLACES whatever preconditioner was attached; a NULL argument leaves the solver with none.
 extern "C" int mk_solver_set_precon_diag(mk_solver *s, const double *diag) {
     MK_ARG(s);
     MK_ARG(MK_ALIGNED16(diag));
     if (diag && !s->takes_precon())
         return mk_fail(MK_ERR_UNSUPPORTED, "this solver kind has no device preconditioner hook");
-    if (s->precon_ilu) {                                     // a diagonal replaces an incomplete factorization
-        mk_ilu_release(s->precon_ilu);
-        s->precon_ilu = nullptr;
-        s->precon_fn = nullptr;
-    }
-    if (s->precon_lbfgs) {                                   // ... and an L-BFGS operator
-        mk_lbfgs_release(s->precon_lbfgs);
-        s->precon_lbfgs = nullptr;
-        s->precon_fn = nullptr;
-    }
+    s->clear_precon();
+    if (diag) s->precon.kind = MK_PRECON_DIAG;
     s->d_prec = diag;
     return MK_OK;
 }
@@ -369,140 +365,66 @@ __global__ __launch_bounds__(MK_BLOCK) void mk_fill_kernel(double *v, int64_t n,
     for (int64_t i = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MK_BLOCK) v[i] = a;
 }
 
-static void mk_drop_precon_ilu(mk_solver *s) {
-    if (s->precon_ilu) mk_ilu_release(s->precon_ilu);
-    s->precon_ilu = nullptr;
-    if (s->precon_lbfgs) mk_lbfgs_release(s->precon_lbfgs);   // (an L-BFGS operator goes wherever a factorization goes)
-    s->precon_lbfgs = nullptr;
+int mk_solver::attach_precon(const MkPrecon &next, const char *who, const char *noun, const char *plural) {
+    if (!takes_precon()) return mk_fail(MK_ERR_UNSUPPORTED, "this solver kind has no preconditioner hook");
+    // what the kind asks of the solver's operator (only a device matrix may be rank local) and of its own size
+    if (next.kind == MK_PRECON_HOST && A->ex.mode >= 0)
+        return mk_fail(MK_ERR_UNSUPPORTED, "host preconditioner callbacks are single-GPU (the vector would have to be gathered)");
+    if (next.kind == MK_PRECON_OBJECT && A->ex.mode >= 0)
+        return mk_fail(MK_ERR_UNSUPPORTED, "%s: %s are single-GPU (the solver's operator carries an exchange plan)", who, plural);
+    if (next.kind == MK_PRECON_OBJECT && next.obj->n != n)
+        return mk_fail(MK_ERR_ARG, "%s: the %s has %lld rows, the solver %lld", who, noun, (long long)next.obj->n, (long long)n);
+    if (next.kind == MK_PRECON_CSR && (next.op->nrows != n || next.op->ncols != n || next.op->ex.mode >= 0))
+        return mk_fail(MK_ERR_ARG, "%s: the preconditioner must be a square device operator of the solver's (local) size %lld "
+                       "without an exchange plan, got %lld x %lld", who, (long long)n, (long long)next.op->nrows,
+                       (long long)next.op->ncols);
+    const size_t len = (size_t)(n > 0 ? n : 1);
+    if (!d_ones) {
+        MK_HIP(hipMalloc((void **)&d_ones, sizeof(double) * len + 16));
+        hipLaunchKernelGGL(mk_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, stream, d_ones, (int64_t)len, 1.0);
+        MK_HIP(hipGetLastError());
+    }
+    if (next.kind == MK_PRECON_HOST && !h_pin) {
+        MK_HIP(hipHostMalloc((void **)&h_pin, sizeof(double) * len, hipHostMallocDefault));
+        MK_HIP(hipHostMalloc((void **)&h_pout, sizeof(double) * len, hipHostMallocDefault));
+    }
+    if (next.kind == MK_PRECON_CSR && !d_ptmp) MK_HIP(hipMalloc((void **)&d_ptmp, sizeof(double) * len + 16));
+    // take the new reference first, then drop the old one: re-setting the attached object must not free it
+    if (next.kind == MK_PRECON_CSR) next.op->dependents += 1;
+    if (next.kind == MK_PRECON_OBJECT) next.obj->hold();
+    clear_precon();
+    precon = next;
+    d_prec = d_ones;
+    return MK_OK;
 }
 
 extern "C" int mk_solver_set_precon_callback(mk_solver *s, mk_precon_fn fn, void *user) {
     MK_ARG(s);
-    if (s->precon_op) mk_release_operand(s->precon_op);
-    s->precon_op = nullptr;
-    mk_drop_precon_ilu(s);
-    if (!fn) {
-        s->precon_fn = nullptr;
-        s->d_prec = nullptr;
-        return MK_OK;
-    }
-    if (!s->takes_precon()) return mk_fail(MK_ERR_UNSUPPORTED, "this solver kind has no preconditioner hook");
-    if (s->A->ex.mode >= 0)
-        return mk_fail(MK_ERR_UNSUPPORTED, "host preconditioner callbacks are single-GPU (the vector would have to be gathered)");
-    const size_t len = (size_t)(s->n > 0 ? s->n : 1);
-    if (!s->d_ones) {
-        MK_HIP(hipMalloc((void **)&s->d_ones, sizeof(double) * len + 16));
-        hipLaunchKernelGGL(mk_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, s->stream, s->d_ones, (int64_t)len, 1.0);
-        MK_HIP(hipGetLastError());
-    }
-    if (!s->h_pin) {
-        MK_HIP(hipHostMalloc((void **)&s->h_pin, sizeof(double) * len, hipHostMallocDefault));
-        MK_HIP(hipHostMalloc((void **)&s->h_pout, sizeof(double) * len, hipHostMallocDefault));
-    }
-    s->precon_fn = fn;
-    s->precon_user = user;
-    s->d_prec = s->d_ones;
-    return MK_OK;
+    if (!fn) return s->clear_precon(), MK_OK;
+    MkPrecon p;
+    p.kind = MK_PRECON_HOST;
+    p.fn = fn;
+    p.user = user;
+    return s->attach_precon(p, "mk_solver_set_precon_callback");
 }
 
 extern "C" int mk_solver_set_precon_csr(mk_solver *s, const mk_csr *M) {
     MK_ARG(s);
-    if (!M) {
-        mk_drop_precon_ilu(s);
-        if (s->precon_op) mk_release_operand(s->precon_op);
-        s->precon_op = nullptr;
-        s->precon_fn = nullptr;
-        s->d_prec = nullptr;
-        return MK_OK;
-    }
-    if (!s->takes_precon()) return mk_fail(MK_ERR_UNSUPPORTED, "this solver kind has no preconditioner hook");
-    if (M->nrows != s->n || M->ncols != s->n || M->ex.mode >= 0)
-        return mk_fail(MK_ERR_ARG, "mk_solver_set_precon_csr: the preconditioner must be a square device operator of the "
-                       "solver's (local) size %lld without an exchange plan, got %lld x %lld", (long long)s->n,
-                       (long long)M->nrows, (long long)M->ncols);
-    const size_t len = (size_t)(s->n > 0 ? s->n : 1);
-    if (!s->d_ones) {
-        MK_HIP(hipMalloc((void **)&s->d_ones, sizeof(double) * len + 16));
-        hipLaunchKernelGGL(mk_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, s->stream, s->d_ones, (int64_t)len, 1.0);
-        MK_HIP(hipGetLastError());
-    }
-    if (!s->d_ptmp) {
-        MK_HIP(hipMalloc((void **)&s->d_ptmp, sizeof(double) * len + 16));
-        MK_HIP(hipMalloc((void **)&s->d_nohalt, 2 * sizeof(int)));
-        MK_HIP(hipMemsetAsync(s->d_nohalt, 0, 2 * sizeof(int), s->stream));
-    }
-    M->dependents += 1;
-    mk_drop_precon_ilu(s);
-    if (s->precon_op) mk_release_operand(s->precon_op);
-    s->precon_op = M;
-    s->precon_fn = mk_precon_on_device;                      // (marks "general preconditioner" at the call sites)
-    s->precon_user = nullptr;
-    s->d_prec = s->d_ones;
-    return MK_OK;
+    if (!M) return s->clear_precon(), MK_OK;
+    MkPrecon p;
+    p.kind = MK_PRECON_CSR;
+    p.op = M;
+    return s->attach_precon(p, "mk_solver_set_precon_csr");
 }
 
-extern "C" int mk_solver_set_precon_ilu(mk_solver *s, const mk_ilu *F) {
+// (the entry points of the objects, mk_solver_set_precon_ilu / _lbfgs, live with their types in mk_ilu.hip / mk_lbfgs.hip)
+int mk_set_precon_object(mk_solver *s, const MkDeviceOp *F, const char *who, const char *noun, const char *plural) {
     MK_ARG(s);
-    if (!F) {
-        mk_drop_precon_ilu(s);
-        s->precon_fn = nullptr;
-        s->d_prec = nullptr;
-        return MK_OK;
-    }
-    if (!s->takes_precon()) return mk_fail(MK_ERR_UNSUPPORTED, "this solver kind has no preconditioner hook");
-    if (s->A->ex.mode >= 0)
-        return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_set_precon_ilu: incomplete factorizations are single-GPU (the solver's "
-                       "operator carries an exchange plan)");
-    if (mk_ilu_rows(F) != s->n)
-        return mk_fail(MK_ERR_ARG, "mk_solver_set_precon_ilu: the factor has %lld rows, the solver %lld",
-                       (long long)mk_ilu_rows(F), (long long)s->n);
-    const size_t len = (size_t)(s->n > 0 ? s->n : 1);
-    if (!s->d_ones) {
-        MK_HIP(hipMalloc((void **)&s->d_ones, sizeof(double) * len + 16));
-        hipLaunchKernelGGL(mk_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, s->stream, s->d_ones, (int64_t)len, 1.0);
-        MK_HIP(hipGetLastError());
-    }
-    mk_ilu_hold(F);                                          // take the new reference first, then drop the old ones
-    mk_drop_precon_ilu(s);
-    if (s->precon_op) mk_release_operand(s->precon_op);
-    s->precon_op = nullptr;
-    s->precon_ilu = F;
-    s->precon_fn = mk_precon_on_device;                      // (marks "general preconditioner" at the call sites)
-    s->precon_user = nullptr;
-    s->d_prec = s->d_ones;
-    return MK_OK;
-}
-
-extern "C" int mk_solver_set_precon_lbfgs(mk_solver *s, const mk_lbfgs *F) {
-    MK_ARG(s);
-    if (!F) {
-        mk_drop_precon_ilu(s);
-        s->precon_fn = nullptr;
-        s->d_prec = nullptr;
-        return MK_OK;
-    }
-    if (!s->takes_precon()) return mk_fail(MK_ERR_UNSUPPORTED, "this solver kind has no preconditioner hook");
-    if (s->A->ex.mode >= 0)
-        return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_set_precon_lbfgs: L-BFGS operators are single-GPU (the solver's "
-                       "operator carries an exchange plan)");
-    if (mk_lbfgs_rows(F) != s->n)
-        return mk_fail(MK_ERR_ARG, "mk_solver_set_precon_lbfgs: the operator has %lld rows, the solver %lld",
-                       (long long)mk_lbfgs_rows(F), (long long)s->n);
-    const size_t len = (size_t)(s->n > 0 ? s->n : 1);
-    if (!s->d_ones) {
-        MK_HIP(hipMalloc((void **)&s->d_ones, sizeof(double) * len + 16));
-        hipLaunchKernelGGL(mk_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, s->stream, s->d_ones, (int64_t)len, 1.0);
-        MK_HIP(hipGetLastError());
-    }
-    mk_lbfgs_hold(F);                                        // take the new reference first, then drop the old ones
-    mk_drop_precon_ilu(s);
-    if (s->precon_op) mk_release_operand(s->precon_op);
-    s->precon_op = nullptr;
-    s->precon_lbfgs = F;
-    s->precon_fn = mk_precon_on_device;                      // (marks "general preconditioner" at the call sites)
-    s->precon_user = nullptr;
-    s->d_prec = s->d_ones;
-    return MK_OK;
+    if (!F) return s->clear_precon(), MK_OK;
+    MkPrecon p;
+    p.kind = MK_PRECON_OBJECT;
+    p.obj = F;
+    return s->attach_precon(p, who, noun, plural);
 }
 
 extern "C" int mk_solver_set_lls_precon(mk_solver *s, const double *diag_m, const double *diag_n) {

@@ -175,7 +175,7 @@ class DeviceRun(object):
     def __init__(self, op, kind, rhs, guess=None, precon_diag=None, **params):
         self.lib = _lib.init()
         self.op = op
-        self.d_prec = None
+        self.precon_kind, self.precon = 'none', None
         # `transpose`: the device operator A.T the least-squares kinds need (mk_solver_set_transpose); their rhs has
         # nrows(A) entries.  `placement_draws`: see _draws().
         transpose = params.pop('transpose', None)
@@ -204,45 +204,36 @@ class DeviceRun(object):
         self.handle = ctypes.c_void_p()
         _lib.check(self.lib.mk_solver_create(op.handle, ctypes.byref(p), ctypes.byref(self.handle)))
         self.transpose = transpose
-        if transpose is not None:
-            try:
-                _lib.check(self.lib.mk_solver_set_transpose(self.handle, transpose.handle))
-            except Exception:
-                self.lib.mk_solver_destroy(self.handle)
-                self.handle = ctypes.c_void_p()
-                raise
-        self.host_precon = None
-        self.device_precon = None
-        self.ilu_precon = None
+        try:                                                 # (no handle may outlive a failed constructor)
+            self.precon_kind, self.precon, self._attach = self._resolve_precon(precon_diag, n)
+            if isinstance(precon_diag, _lib.DeviceArray):    # (a diagonal already resident in HBM: the caller's)
+                self._borrowed.append(precon_diag)
+            self._apply_precon(self.handle)
+        except Exception:
+            self.lib.mk_solver_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+            raise
+        self.result = _lib.MkResult()
+        self._setup_done = False
+        self.placement = {"count": 1, "chosen": 0, "per_draw_ms_per_pass": [], "probe_seconds": 0.0, "passes_per_draw": 0}
+
+    def _resolve_precon(self, precon, n):
+        """The one preconditioner of this run, as `_device_precon` returned it: its kind, the object to keep alive (for a
+        diagonal the DeviceArray, which `close` frees unless it is the caller's) and the call that attaches it to a solver
+        handle (the constructor's, and every placement draw's)."""
+        lib = self.lib
         from .tools import IluPreconditioner
-        if isinstance(precon_diag, IluPreconditioner):
-            self.ilu_precon, precon_diag = precon_diag, None
-            try:
-                _lib.check(self.lib.mk_solver_set_precon_ilu(self.handle, self.ilu_precon._live()))
-            except Exception:
-                self.lib.mk_solver_destroy(self.handle)
-                self.handle = ctypes.c_void_p()
-                raise
-        self.lbfgs_precon = None
         from .lbfgs import InverseLBFGSOperator
-        if isinstance(precon_diag, InverseLBFGSOperator) and precon_diag._is_inverse:
-            self.lbfgs_precon, precon_diag = precon_diag, None
-            try:
-                _lib.check(self.lib.mk_solver_set_precon_lbfgs(self.handle, self.lbfgs_precon._live()))
-            except Exception:
-                self.lib.mk_solver_destroy(self.handle)
-                self.handle = ctypes.c_void_p()
-                raise
-        if isinstance(precon_diag, DevicePrecon):
-            self.device_precon, precon_diag = precon_diag, None
-            try:
-                _lib.check(self.lib.mk_solver_set_precon_csr(self.handle, self.device_precon.dev.handle))
-            except Exception:
-                self.lib.mk_solver_destroy(self.handle)      # (no handle may outlive a failed constructor)
-                self.handle = ctypes.c_void_p()
-                raise
-        if isinstance(precon_diag, HostPrecon):
-            hp, self.host_precon, precon_diag = precon_diag, precon_diag, None
+        if precon is None:
+            return 'none', None, lambda handle: 0
+        if isinstance(precon, IluPreconditioner):
+            return 'ilu', precon, lambda handle: lib.mk_solver_set_precon_ilu(handle, precon._live())
+        if isinstance(precon, InverseLBFGSOperator) and precon._is_inverse:
+            return 'lbfgs', precon, lambda handle: lib.mk_solver_set_precon_lbfgs(handle, precon._live())
+        if isinstance(precon, DevicePrecon):
+            return 'device', precon, lambda handle: lib.mk_solver_set_precon_csr(handle, precon.dev.handle)
+        if isinstance(precon, HostPrecon):
+            hp = precon
 
             def call(user, rp, yp):
                 try:
@@ -257,28 +248,18 @@ class DeviceRun(object):
                     if hp.error is None:                    # (keep the root cause, not a follow-up failure)
                         hp.error = exc
                     return 1
-            self._precon_cb = _lib.PRECON_FN(call)          # keep the thunk alive
-            try:
-                _lib.check(self.lib.mk_solver_set_precon_callback(self.handle, self._precon_cb, None))
-            except Exception:
-                self.lib.mk_solver_destroy(self.handle)      # (no handle may outlive a failed constructor)
-                self.handle = ctypes.c_void_p()
-                raise
-        if precon_diag is not None:
-            self.d_prec = precon_diag if isinstance(precon_diag, _lib.DeviceArray) else \
-                _lib.DeviceArray.from_numpy(as_f64_vector(precon_diag, n, 'precon.diag'))
-            if isinstance(precon_diag, _lib.DeviceArray):
-                self._borrowed.append(precon_diag)
-            _lib.check(self.lib.mk_solver_set_precon_diag(self.handle, self.d_prec.ptr))
-        self.result = _lib.MkResult()
-        self._setup_done = False
-        self.placement = {"count": 1, "chosen": 0, "per_draw_ms_per_pass": [], "probe_seconds": 0.0, "passes_per_draw": 0}
+            cb = _lib.PRECON_FN(call)                       # (the closure below keeps the thunk alive)
+            return 'host', hp, lambda handle: lib.mk_solver_set_precon_callback(handle, cb, None)
+        # a diagonal: a DeviceArray already resident in HBM, or a host array (copied there)
+        d = precon if isinstance(precon, _lib.DeviceArray) else \
+            _lib.DeviceArray.from_numpy(as_f64_vector(precon, n, 'precon.diag'))
+        return 'diag', d, lambda handle: lib.mk_solver_set_precon_diag(handle, d.ptr)
 
     def _check(self, rc):
         if rc != 0 and hasattr(self.op, 'raise_pending'):
             self.op.raise_pending()                           # what a matrix-free operator raised in its callback
-        if rc != 0 and self.host_precon is not None and self.host_precon.error is not None:
-            err, self.host_precon.error = self.host_precon.error, None
+        if rc != 0 and self.precon_kind == 'host' and self.precon.error is not None:
+            err, self.precon.error = self.precon.error, None
             raise err
         _lib.check(rc)
 
@@ -319,7 +300,7 @@ class DeviceRun(object):
         min_mb = float(os.environ.get('MK_PLACEMENT_MIN_MB', '256'))      # (tests lower it to draw on small problems)
         if want <= 1 or 8 * self.n <= min_mb * 1024 * 1024:
             return 1
-        if getattr(self.op, 'local_size', None) is not None or self.host_precon is not None:
+        if getattr(self.op, 'local_size', None) is not None or self.precon_kind == 'host':
             return 1
         from .linop import CsrOperator
         if not isinstance(self.op, CsrOperator):             # (matrix-free shells: every pass calls back to the host)
@@ -335,14 +316,7 @@ class DeviceRun(object):
     def _apply_precon(self, handle):
         if getattr(self, 'transpose', None) is not None:
             _lib.check(self.lib.mk_solver_set_transpose(handle, self.transpose.handle))
-        if self.device_precon is not None:
-            _lib.check(self.lib.mk_solver_set_precon_csr(handle, self.device_precon.dev.handle))
-        if self.ilu_precon is not None:
-            _lib.check(self.lib.mk_solver_set_precon_ilu(handle, self.ilu_precon._live()))
-        if self.lbfgs_precon is not None:
-            _lib.check(self.lib.mk_solver_set_precon_lbfgs(handle, self.lbfgs_precon._live()))
-        if self.d_prec is not None:
-            _lib.check(self.lib.mk_solver_set_precon_diag(handle, self.d_prec.ptr))
+        _lib.check(self._attach(handle))
 
     def _timed_passes(self, handle, warm=4, passes=12):
         g = None if self.d_guess is None else self.d_guess.ptr
@@ -466,7 +440,8 @@ class DeviceRun(object):
         if getattr(self, 'handle', None) is not None and self.handle.value:
             self.lib.mk_solver_destroy(self.handle)
             self.handle = ctypes.c_void_p()
-        for b in (self.d_rhs, self.d_guess, getattr(self, 'd_prec', None)):
+        diag = self.precon if getattr(self, 'precon_kind', None) == 'diag' else None
+        for b in (self.d_rhs, self.d_guess, diag):
             if b is not None and not any(b is x for x in getattr(self, '_borrowed', [])):
                 b.free()
 

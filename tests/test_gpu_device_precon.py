@@ -109,3 +109,126 @@ def test_block_preconditioner_of_device_matrices_and_wrong_shapes():
         pykrylov_amd.BiCGSTAB(op, precon=M1).solve(rhs)
     for o in (op, Mop, M1, M2):
         o.free()
+
+
+@pytest.mark.parametrize("solver", ["cg", "bicgstab"])
+def test_every_setter_replaces_whatever_preconditioner_was_attached(solver):
+    """One solver walks through the attachments of the C ABI -- device matrix, incomplete factor, L-BFGS operator, host
+    callback, diagonal, NULL -- and solves after each step: history and iterate must have the bits of a fresh solver that
+    was only ever given that one preconditioner (so nothing of the previous attachment acts on), and consecutive steps
+    must differ (so the comparison can see a preconditioner that stayed).  Then a factor and an L-BFGS operator are
+    destroyed while the solver holds them and replaced on it."""
+    import ctypes
+    from pykrylov_amd import _lib
+    from pykrylov_amd.generic import DeviceRun
+    A, op, Mop, Mref, rhs = problem(12)                                      # SPD, n = 720
+    n = A.shape[0]
+    lib = _lib.init()
+    rng = np.random.default_rng(11)
+    kind = dict(cg=_lib.MK_CG, bicgstab=_lib.MK_BICGSTAB)[solver]
+
+    def factor():
+        h = ctypes.c_void_p()
+        _lib.check((lib.mk_ic0_create if solver == "cg" else lib.mk_ilu0_create)(op.handle, ctypes.byref(h)))
+        return h
+
+    def lbfgs():                                                             # three pairs (s, A s): an SPD inverse
+        h = ctypes.c_void_p()
+        _lib.check(lib.mk_lbfgs_create(n, 3, 1, ctypes.byref(h)))
+        for _ in range(3):
+            s = rng.standard_normal(n)
+            ds, dy = _lib.DeviceArray.from_numpy(s), _lib.DeviceArray.from_numpy(A.matvec(s))
+            ok = ctypes.c_int32(0)
+            _lib.check(lib.mk_lbfgs_store(h, ds.ptr, dy.ptr, 1e-20, ctypes.byref(ok)))
+            assert ok.value == 1
+            ds.free()
+            dy.free()
+        return h
+
+    F, H = factor(), lbfgs()
+    dinv = 1.0 / A.to_dense().diagonal()
+    d_dinv = _lib.DeviceArray.from_numpy(dinv)
+    calls = [0]
+
+    def call(user, rp, yp):                                                  # a scaled Jacobi on the host
+        r = np.ctypeslib.as_array(ctypes.cast(rp, ctypes.POINTER(ctypes.c_double)), shape=(n,))
+        np.ctypeslib.as_array(ctypes.cast(yp, ctypes.POINTER(ctypes.c_double)), shape=(n,))[:] = 0.75 * dinv * r
+        calls[0] += 1
+        return 0
+    cb = _lib.PRECON_FN(call)
+    steps = [("device matrix", lambda h: lib.mk_solver_set_precon_csr(h, Mop.handle)),
+             ("factor", lambda h: lib.mk_solver_set_precon_ilu(h, F)),
+             ("lbfgs", lambda h: lib.mk_solver_set_precon_lbfgs(h, H)),
+             ("callback", lambda h: lib.mk_solver_set_precon_callback(h, cb, None)),
+             ("diagonal", lambda h: lib.mk_solver_set_precon_diag(h, d_dinv.ptr)),
+             ("null", lambda h: lib.mk_solver_set_precon_csr(h, None))]
+
+    def new_run():
+        return DeviceRun(op, kind, rhs, abstol=0.0, reltol=1e-10, matvec_max=60)
+
+    def solve(run):
+        res = run.run()
+        return int(res.nMatvec), run.history(), run.x()
+
+    def same(a, b):
+        return a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+
+    walker, prev, alone = new_run(), None, {}
+    for name, attach in steps:
+        _lib.check(attach(walker.handle))
+        got = solve(walker)
+        fresh = new_run()
+        _lib.check(attach(fresh.handle))
+        want = solve(fresh)
+        fresh.close()
+        assert got[0] > 3 and np.all(np.isfinite(got[2])), (solver, name)       # (BiCGSTAB keeps no history)
+        assert same(got, want), (solver, name)
+        assert prev is None or not same(got, prev), (solver, name)
+        prev = alone[name] = got
+    assert calls[0] > 3
+    plain = prev
+
+    # ... and every ordered pair a -> b of the six, the walk's order or not (device matrix -> diagonal among them), with the
+    # NULL of every setter in turn
+    nulls = [lambda h: lib.mk_solver_set_precon_diag(h, None),
+             lambda h: lib.mk_solver_set_precon_callback(h, _lib.PRECON_FN(), None),        # (a NULL function pointer)
+             lambda h: lib.mk_solver_set_precon_csr(h, None), lambda h: lib.mk_solver_set_precon_ilu(h, None),
+             lambda h: lib.mk_solver_set_precon_lbfgs(h, None)]
+    for k, (a, attach_a) in enumerate(steps[:5]):
+        for b, attach_b in steps[:5] + [("null", nulls[k])]:
+            if a != b:
+                run = new_run()
+                _lib.check(attach_a(run.handle))
+                assert same(solve(run), alone[a]), (solver, a)
+                _lib.check(attach_b(run.handle))
+                assert same(solve(run), alone[b]), (solver, a, b)
+                run.close()
+
+    # destroyed while held: the solver keeps applying the object until it is replaced, which frees it
+    _lib.check(lib.mk_solver_set_precon_ilu(walker.handle, F))
+    _lib.check(lib.mk_solver_set_precon_ilu(walker.handle, F))               # (re-setting the attached object keeps it)
+    with_f = solve(walker)
+    small = ctypes.c_void_p()
+    _lib.check(lib.mk_lbfgs_create(n - 1, 3, 1, ctypes.byref(small)))
+    assert lib.mk_solver_set_precon_lbfgs(walker.handle, small) == -2       # MK_ERR_ARG: a setter that fails changes nothing
+    _lib.check(lib.mk_lbfgs_destroy(small))
+    assert same(solve(walker), with_f)
+    _lib.check(lib.mk_ilu_destroy(F))
+    assert same(solve(walker), with_f)
+    _lib.check(lib.mk_solver_set_precon_lbfgs(walker.handle, H))             # F goes here
+    with_h = solve(walker)
+    _lib.check(lib.mk_lbfgs_destroy(H))
+    assert same(solve(walker), with_h) and not same(with_h, with_f)
+    _lib.check(lib.mk_solver_set_precon_diag(walker.handle, None))           # H goes here
+    assert same(solve(walker), plain)
+    F2, H2 = factor(), lbfgs()                                               # later creations work
+    _lib.check(lib.mk_solver_set_precon_ilu(walker.handle, F2))
+    assert same(solve(walker), with_f)
+    _lib.check(lib.mk_solver_set_precon_lbfgs(walker.handle, H2))
+    assert np.all(np.isfinite(solve(walker)[2]))
+    walker.close()
+    _lib.check(lib.mk_ilu_destroy(F2))
+    _lib.check(lib.mk_lbfgs_destroy(H2))
+    d_dinv.free()
+    op.free()
+    Mop.free()
