@@ -526,15 +526,38 @@ MK_API int mk_lbfgs_download(const mk_lbfgs *F, double *s_host, double *y_host);
 MK_API int mk_solver_set_precon_lbfgs(mk_solver *s, const mk_lbfgs *F);
 /* The least-squares kinds take two preconditioners, applied by the reference as `u = M(Mu)` in the m-space and
  * `v = N(Nv)` in the n-space of the Golub-Kahan process (lls/lsqr.py:189-190,201-202,253-254,265-266 and the same
- * lines of lsmr.py, craig.py, craigmr.py): device arrays with the diagonals of M (nrows(A) entries) and N
- * (ncols(A) entries), either may be NULL; borrowed until the solver is destroyed.  Call before mk_solver_setup. */
+ * lines of lsmr.py, craig.py, craigmr.py).  Each side holds ONE preconditioner of any of the kinds the square solvers
+ * take -- a diagonal, a host callback, a device matrix or composite, an incomplete factorization, an inverse L-BFGS
+ * operator -- and every setter below replaces what its side held (releasing the reference it kept on a matrix or object)
+ * without touching the other side.  MK_ERR_UNSUPPORTED for the six square solvers.  Call before mk_solver_setup.
+ *
+ * Diagonals: device arrays with the diagonals of M (nrows(A) entries) and N (ncols(A) entries), multiplied inside the
+ * kernels; borrowed until the solver is destroyed.  A NULL side loses a diagonal set earlier and keeps anything else. */
 MK_API int mk_solver_set_lls_precon(mk_solver *s, const double *diag_m, const double *diag_n);
 /* M and / or N as HOST callbacks `fn(user, in_host, out_host)` -- any callable the reference would apply as
- * `u = M(Mu)` (nrows(A) entries) or `v = N(Nv)` (ncols(A) entries); a NULL function leaves that side to
- * mk_solver_set_lls_precon.  The loop stays on the device: the vector is copied to the host right after the kernel that
- * formed it, the callback's result replaces u / v and <u, Mu> / <v, Nv> are re-formed on the device.  Not invoked once
- * the loop has halted, nor for N when beta = 0 (lsqr.py:258).  Single GPU.  Call before mk_solver_setup. */
+ * `u = M(Mu)` (nrows(A) entries) or `v = N(Nv)` (ncols(A) entries); a NULL function removes a callback set earlier and
+ * leaves anything else on that side.  The loop stays on the device: the vector is copied to the host right after the kernel
+ * that formed it, the callback's result replaces u / v and <u, Mu> / <v, Nv> are re-formed on the device.  Not invoked once
+ * the loop has halted, nor for N when beta = 0 (lsqr.py:258).  Single GPU. */
 MK_API int mk_solver_set_lls_precon_callback(mk_solver *s, mk_precon_fn fn_m, void *user_m, mk_precon_fn fn_n, void *user_n);
+/* M or N (`side`) as a DEVICE preconditioner, applied at the sites of the callback without leaving HBM and with its bits:
+ * u / v is replaced right after the kernel that formed Mu / Nv and <u, Mu> / <v, Nv> is re-formed in the same order.  Every
+ * launch obeys the loop's halt words (nothing changes once the loop has ended), and N is not applied when beta = 0
+ * (lsqr.py:258) -- both decided on the device, without a host read.
+ *   _csr:   a device matrix or composite (e.g. pykrylov_amd.tools.block_jacobi), square, of that side's size (nrows(A) for
+ *           M, ncols(A) for N), without an exchange plan; counted among the matrix's dependents while the side holds it.
+ *   _ilu:   an incomplete factorization (mk_ilu0_create / mk_ic0_create) of that side's size.
+ *   _bfgs:  an inverse L-BFGS operator (mk_lbfgs) of that side's size; a pair stored between two solves is seen by the
+ *           next one.  (Spelt _bfgs on purpose: the names that contain "lbfgs" are the operator's own entry points and the
+ *           square solvers' mk_solver_set_precon_lbfgs, a closed set that tests/test_lbfgs_cpu.py pins name by name.)
+ * The solver holds a factor or operator until it is destroyed or the side is given something else: destroying the object
+ * meanwhile is deferred.  NULL removes what the side holds.  MK_ERR_ARG on a size mismatch or a non-square matrix.
+ * Single GPU: with row blocks over several GPUs (mk_csr_set_row_block) only diagonals are supported, mk_solver_setup fails
+ * with MK_ERR_UNSUPPORTED otherwise. */
+enum { MK_LLS_SIDE_M = 0, MK_LLS_SIDE_N = 1 };
+MK_API int mk_solver_set_lls_precon_csr(mk_solver *s, int side, const mk_csr *P);
+MK_API int mk_solver_set_lls_precon_ilu(mk_solver *s, int side, const mk_ilu *F);
+MK_API int mk_solver_set_lls_precon_bfgs(mk_solver *s, int side, const mk_lbfgs *F);
 /* Everything before the `while` loop of the reference's solve().  rhs_dev has n_local
  * entries; guess_dev may be NULL (x0 = 0).  Neither is modified. */
 MK_API int mk_solver_setup(mk_solver *s, const double *rhs_dev, const double *guess_dev);

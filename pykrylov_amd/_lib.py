@@ -151,6 +151,9 @@ PROTOTYPES = {
     "mk_solver_set_precon_lbfgs": (ctypes.c_int, [c_vp, c_vp]),
     "mk_solver_set_lls_precon_callback": (ctypes.c_int, [c_vp, PRECON_FN, c_vp, PRECON_FN, c_vp]),
     "mk_solver_set_lls_precon": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mk_solver_set_lls_precon_csr": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
+    "mk_solver_set_lls_precon_ilu": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
+    "mk_solver_set_lls_precon_bfgs": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
     "mk_solver_setup": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mk_solver_iterate": (ctypes.c_int, [c_vp, c_i64, P(c_i64)]),
     "mk_solver_finish": (ctypes.c_int, [c_vp, P(MkResult)]),

@@ -395,6 +395,10 @@ extern "C" int mk_solver_set_precon_ilu(mk_solver *s, const mk_ilu *F) {
     return mk_set_precon_object(s, F, "mk_solver_set_precon_ilu", "factor", "incomplete factorizations");
 }
 
+extern "C" int mk_solver_set_lls_precon_ilu(mk_solver *s, int side, const mk_ilu *F) {
+    return mk_lls_set_precon_object(s, side, F, "mk_solver_set_lls_precon_ilu", "factor");
+}
+
 extern "C" int mk_ilu_apply(const mk_ilu *F, const double *in_dev, double *out_dev) {
     MK_REQUIRE_INIT();
     MK_ARG(F && (F->n == 0 || (in_dev && out_dev)));

@@ -1,4 +1,4 @@
-// mk_lls.hip -- LSQR, LSMR, CRAIG, CRAIG-MR, device resident; M and N may be diagonal preconditioners.
+// mk_lls.hip -- LSQR, LSMR, CRAIG, CRAIG-MR, device resident; M and N are preconditioner slots of every kind (mk_solver.h).
 // Reference: pykrylov/lls/lsqr.py:86-453, lsmr.py:64-492, craig.py:104-520, craigmr.py:51-241.
 //
 // All four run on the Golub-Kahan bidiagonalisation (lsqr.py:252-271): with u, v normalised in place,
@@ -203,6 +203,33 @@ struct OpScaleNv {   // Nv /= alpha where the solver's G4 did v /= alpha (lsqr.p
         mk_st2(Nv, i, w);
     }
     __device__ void one(int64_t i, double *) { Nv[i] = Nv[i] / alpha; }
+};
+
+// N as a device object: its launches cannot wait for beta, so t = N(Nv) is formed out of place and taken here under the
+// condition of the site (lsqr.py:258) and the halt word, with <v, Nv> in the order of MkOpDot<SLOT_VV> on (v, Nv)
+struct OpTakeV {     // if beta > 0: v = t ; <v, Nv>
+    static constexpr int NACC = 1, SLOT0 = SLOT_VV;
+    static constexpr bool NO_MARCH = true;         // (rectangular operators: mk_device.h MkNoMarch)
+    const double *scal;
+    const double *t, *Nv;
+    double *v;
+    bool on;
+    __device__ bool prologue(double *, bool) {
+        on = scal[S_BETA] > 0;
+        return false;
+    }
+    __device__ bool skip() const { return !on; }
+    __device__ void pair(int64_t i, double *acc) {
+        const double2 a = mk_ld2(t, i), b = mk_ld2(Nv, i);
+        mk_st2(v, i, a);
+        acc[0] += a.x * b.x;
+        acc[0] += a.y * b.y;
+    }
+    __device__ void one(int64_t i, double *acc) {
+        const double a = t[i];
+        v[i] = a;
+        acc[0] += a * Nv[i];
+    }
 };
 
 // new alpha exactly as the reference leaves it: unchanged when beta == 0
@@ -991,90 +1018,73 @@ struct LlsSolver : mk_solver {
     const double *d_dm = nullptr, *d_dn = nullptr; // diagonals of M (m entries) and N (n entries), borrowed
     int np_A = 1, np_At = 1, np_n = 1, np_m = 1;
     int64_t itnlim = 0;
-    // M / N as host callbacks (mk_solver_set_lls_precon_callback): the kernels run with a diagonal of ones and the
-    // vector `u = M(Mu)` / `v = N(Nv)` is replaced by the callback's result right after the kernel that formed it;
-    // <u, Mu> / <v, Nv> are then re-formed by a dot kernel (same scheme as mk_solver::apply_precon)
-    mk_precon_fn fn_m = nullptr, fn_n = nullptr;
-    void *user_m = nullptr, *user_n = nullptr;
-    double *d_ones_m = nullptr, *d_ones_n = nullptr, *h_cb_in = nullptr, *h_cb_out = nullptr;
-    int64_t cb_cap = 0;
+    // M and N (mk_solver_set_lls_precon*): a diagonal is multiplied inside the kernels (d_dm / d_dn).  With a general kind
+    // the kernels run with a diagonal of ones and `u = M(Mu)` / `v = N(Nv)` is replaced by mk_solver::apply_slot's result
+    // right after the kernel that formed Mu / Nv; <u, Mu> / <v, Nv> are then re-formed in the stream kernels' order
+    MkPrecon pm, pn;
+    double *d_ones_m = nullptr, *d_ones_n = nullptr;
+    double *d_ntmp = nullptr;                    // N(Nv) of a device object before it is taken (OpTakeV)
 
     ~LlsSolver() override {
+        if (mk_ctx().ready) hipStreamSynchronize(mk_ctx().stream);   // (an object released below may free its memory)
+        pm.release();
+        pn.release();
         hipFree(d_ones_m);
         hipFree(d_ones_n);
-        if (h_cb_in) hipHostFree(h_cb_in);
-        if (h_cb_out) hipHostFree(h_cb_out);
     }
 
-    // out = fn(in) on the host.  Skipped once the loop has halted (unless `force`: the setup calls) and when the
-    // product that formed `in` did not run (`need_beta`: lsqr.py:258, everything about v happens `if beta > 0`).
-    int host_apply(mk_precon_fn fn, void *user, const double *in_dev, double *out_dev, int64_t len, bool force,
-                   bool need_beta) {
-        int h = 0;
-        double beta = 1.0;
-        MK_HIP(hipMemcpyAsync(&h, d_halt + (q & 1), sizeof(int), hipMemcpyDeviceToHost, stream));
-        if (need_beta) MK_HIP(hipMemcpyAsync(&beta, d_scal + S_BETA, sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (len > 0) MK_HIP(hipMemcpyAsync(h_cb_in, in_dev, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, stream));
-        MK_HIP(hipStreamSynchronize(stream));
-        if ((h && !force) || !(beta > 0)) return MK_OK;
-        if (fn(user, h_cb_in, h_cb_out) != 0) {
-            const int rc = mk_fail(MK_ERR_STATE, "the host preconditioner callback (M or N) reported a failure");
-            if (mk_ctx().pending_rc == MK_OK) mk_ctx().pending_rc = rc;
-            return rc;
-        }
-        if (len > 0) MK_HIP(hipMemcpyAsync(out_dev, h_cb_out, sizeof(double) * (size_t)len, hipMemcpyHostToDevice, stream));
-        return MK_OK;
-    }
-    // <v, Nv> comes from the A' product's epilogue, or from the dot kernel that follows an N callback
-    int np_vv() const { return fn_n ? np_n : np_At; }
+    // <v, Nv> comes from the A' product's epilogue, or from the stream kernel that follows a general N
+    int np_vv() const { return pn.general() ? np_n : np_At; }
     int apply_M(bool force) {                    // u = M(Mu) ; <u, Mu>
-        if (!fn_m) return MK_OK;
-        int rc = host_apply(fn_m, user_m, d_Mu, d_u, m, force, false);
+        if (!pm.general()) return MK_OK;
+        int rc = apply_slot(pm, m, d_Mu, d_u, force);
         if (rc != MK_OK) return rc;
         mk_launch_stream(this, MkOpDot<SLOT_UU>{d_u, d_Mu}, m);
         return MK_OK;
     }
-    int apply_N(bool force) {                    // v = N(Nv) ; <v, Nv>
-        if (!fn_n) return MK_OK;
-        int rc = host_apply(fn_n, user_n, d_Nv, d_v, nn, force, true);
+    // v = N(Nv) ; <v, Nv> -- only if beta > 0 (lsqr.py:258: the product that formed Nv did not run otherwise, and Nv has been
+    // rescaled since v was formed).  A callback reads beta with the halt word; a device matrix is multiplied under the A'
+    // product's own gate, straight into v; a device object's result is taken by OpTakeV.
+    int apply_N(bool force) {
+        if (!pn.general()) return MK_OK;
+        if (pn.kind == MK_PRECON_OBJECT) {
+            int rc = apply_slot(pn, nn, d_Nv, d_ntmp, force);
+            if (rc != MK_OK) return rc;
+            mk_launch_stream(this, OpTakeV{d_scal, d_ntmp, d_Nv, d_v, false}, nn);
+            return MK_OK;
+        }
+        int rc = pn.kind == MK_PRECON_CSR ? mk_apply_csr_slot(this, pn.op, nn, d_Nv, d_v, force, GateV{d_scal})
+                                          : apply_slot(pn, nn, d_Nv, d_v, force, d_scal + S_BETA);
         if (rc != MK_OK) return rc;
         mk_launch_stream(this, MkOpDot<SLOT_VV>{d_v, d_Nv}, nn);
         return MK_OK;
     }
-    int set_callbacks(mk_precon_fn fm, void *um, mk_precon_fn fn, void *un) {
-        const int64_t mm = A->nrows, nc = A->ncols, cap = mm > nc ? mm : nc;
-        if ((fm || fn) && cap > cb_cap) {
-            if (h_cb_in) hipHostFree(h_cb_in);
-            if (h_cb_out) hipHostFree(h_cb_out);
-            h_cb_in = h_cb_out = nullptr;
-            MK_HIP(hipHostMalloc((void **)&h_cb_in, sizeof(double) * (size_t)(cap > 0 ? cap : 1), hipHostMallocDefault));
-            MK_HIP(hipHostMalloc((void **)&h_cb_out, sizeof(double) * (size_t)(cap > 0 ? cap : 1), hipHostMallocDefault));
-            cb_cap = cap;
-        }
-        auto ones = [&](double **p, int64_t len) -> int {
-            if (*p) return MK_OK;
-            MK_HIP(hipMalloc((void **)p, sizeof(double) * (size_t)(len > 0 ? len : 1) + 16));
-            hipLaunchKernelGGL(lls_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, stream, *p, len, 1.0);
+    int set_side(int side, const MkPrecon &next, const double *diag, const char *who, const char *noun) {
+        MkPrecon &slot = side ? pn : pm;
+        const double *&dd = side ? d_dn : d_dm;
+        double *&ones = side ? d_ones_n : d_ones_m;
+        const int64_t mm = A->nrows, nc = A->ncols, len = side ? nc : mm, cap = mm > nc ? mm : nc;
+        const char *name = side ? "N" : "M";
+        if (next.kind == MK_PRECON_OBJECT && next.obj->n != len)
+            return mk_fail(MK_ERR_ARG, "%s: the %s has %lld rows, %s takes vectors of %lld entries", who, noun,
+                           (long long)next.obj->n, name, (long long)len);
+        if (next.kind == MK_PRECON_CSR && (next.op->nrows != len || next.op->ncols != len || next.op->ex.mode >= 0))
+            return mk_fail(MK_ERR_ARG, "%s: %s must be a square device operator of size %lld without an exchange plan, got "
+                           "%lld x %lld", who, name, (long long)len, (long long)next.op->nrows, (long long)next.op->ncols);
+        if (next.general() && !ones) {
+            MK_HIP(hipMalloc((void **)&ones, sizeof(double) * (size_t)(len > 0 ? len : 1) + 16));
+            hipLaunchKernelGGL(lls_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, stream, ones, len, 1.0);
             MK_HIP(hipGetLastError());
-            return MK_OK;
-        };
-        int rc;
-        if (fm) {
-            if ((rc = ones(&d_ones_m, mm)) != MK_OK) return rc;
-            d_dm = d_ones_m;
-        } else if (fn_m) {
-            d_dm = nullptr;
         }
-        if (fn) {
-            if ((rc = ones(&d_ones_n, nc)) != MK_OK) return rc;
-            d_dn = d_ones_n;
-        } else if (fn_n) {
-            d_dn = nullptr;
+        if (next.kind == MK_PRECON_HOST && !h_pin) {         // (one pair of pinned buffers serves both sides)
+            MK_HIP(hipHostMalloc((void **)&h_pin, sizeof(double) * (size_t)(cap > 0 ? cap : 1), hipHostMallocDefault));
+            MK_HIP(hipHostMalloc((void **)&h_pout, sizeof(double) * (size_t)(cap > 0 ? cap : 1), hipHostMallocDefault));
         }
-        fn_m = fm;
-        user_m = um;
-        fn_n = fn;
-        user_n = un;
+        // take the new reference first, then drop the old one: re-setting the attached object must not free it
+        next.hold();
+        slot.release();
+        slot = next;
+        dd = next.general() ? ones : (next.kind == MK_PRECON_DIAG ? diag : nullptr);
         return MK_OK;
     }
 
@@ -1126,9 +1136,9 @@ struct LlsSolver : mk_solver {
                            "not with a halo / all-gather exchange plan");
         dist = A->row_block && mk_comm_active();
         sliced = dist && A->row_block == 2;
-        if (dist && (A->host_fn || At->host_fn || fn_m || fn_n))
-            return mk_fail(MK_ERR_UNSUPPORTED, "least-squares solvers: matrix-free operators and M / N callbacks are "
-                           "single-GPU");
+        if (dist && (A->host_fn || At->host_fn || pm.general() || pn.general()))
+            return mk_fail(MK_ERR_UNSUPPORTED, "least-squares solvers: matrix-free operators and M / N other than "
+                           "diagonals are single-GPU");
         if (prm.window < 1 || prm.window > MAXWIN) return mk_fail(MK_ERR_ARG, "window must be in 1..%d", MAXWIN);
         use_hist2 = true;
         m = A->nrows;
@@ -1171,6 +1181,7 @@ struct LlsSolver : mk_solver {
         int rc2;
         if (d_dm && !d_Mu && (rc2 = alloc_vec(&d_Mu, m))) return rc2;
         if (d_dn && !d_Nv && (rc2 = alloc_vec(&d_Nv, nA))) return rc2;
+        if (pn.kind == MK_PRECON_OBJECT && !d_ntmp && (rc2 = alloc_vec(&d_ntmp, nn))) return rc2;
         if (dist && !d_t && (rc2 = alloc_vec(&d_t, nF))) return rc2;          // (entries past nn stay zero)
         if (sliced && !d_tl && ((rc2 = alloc_vec(&d_tl, cnt)) || (rc2 = alloc_vec(&d_xfull, nF)))) return rc2;
         if (d_Nv) MK_HIP(hipMemsetAsync(d_Nv, 0, sizeof(double) * (size_t)nA, stream));
@@ -1224,7 +1235,7 @@ struct LlsSolver : mk_solver {
         int rc = apply_M(false);
         if (rc != MK_OK) return rc;
         if ((rc = sum_uu()) != MK_OK) return rc;
-        mk_launch_stream(this, OpNormU{d_part, fn_m ? np_m : np_A, d_scal, d_u, d_dm ? d_Mu : nullptr, 0.0}, m);   // G2
+        mk_launch_stream(this, OpNormU{d_part, pm.general() ? np_m : np_A, d_scal, d_u, d_dm ? d_Mu : nullptr, 0.0}, m);   // G2
         if ((rc = product_At(false)) != MK_OK) return rc;                                                // G3
         if (kind == MK_LSQR) {
             mk_launch_stream(this, lsqr::OpN{d_part, np_vv(), d_scal, d_status, d_hist, par, itn, prm.window, prm.damp,
@@ -1275,21 +1286,17 @@ struct LlsSolver : mk_solver {
 
     const double *x() const override { return (sliced && kind != MK_CRAIGMR) ? d_xfull : d_x; }
     const double *vector(int i) const override { return i == 0 ? d_r : (i == 1 ? d_u : (i == 2 ? d_v : nullptr)); }
-    int set_metric(const double *dm, const double *dn) {
-        if (!fn_m) d_dm = dm;                    // (a side that has a callback keeps its diagonal of ones)
-        if (!fn_n) d_dn = dn;
-        return MK_OK;
-    }
 };
 
 }  // namespace
 
 mk_solver *mk_make_lls(int kind) { return new LlsSolver(kind); }
 
-int mk_lls_set_metric(mk_solver *s, const double *dm, const double *dn) {
-    return static_cast<LlsSolver *>(s)->set_metric(dm, dn);
+int mk_lls_set_side(mk_solver *s, int side, const MkPrecon &next, const double *diag, const char *who, const char *noun) {
+    return static_cast<LlsSolver *>(s)->set_side(side, next, diag, who, noun);
 }
 
-int mk_lls_set_callbacks(mk_solver *s, mk_precon_fn fn_m, void *user_m, mk_precon_fn fn_n, void *user_n) {
-    return static_cast<LlsSolver *>(s)->set_callbacks(fn_m, user_m, fn_n, user_n);
+int mk_lls_side_kind(const mk_solver *s, int side) {
+    const LlsSolver *l = static_cast<const LlsSolver *>(s);
+    return side ? l->pn.kind : l->pm.kind;
 }

@@ -51,17 +51,19 @@ struct MkDeviceOp {
     }
 };
 
-// The one preconditioner a solver carries.  A diagonal is multiplied inside the loop's kernels (mk_solver::d_prec).  With
-// one of the general kinds the kernels run with a diagonal of ones (`1.0 * v` is exact) and every preconditioned vector is
-// replaced by `apply_precon`'s result right after the kernel that produced it; inner products with it are re-formed by a
-// separate dot kernel.
+// A preconditioner slot: the one a square solver carries (mk_solver::precon), and each of M and N of a least-squares solver
+// (mk_lls.hip).  A diagonal is multiplied inside the loop's kernels (mk_solver::d_prec; d_dm / d_dn).  With one of the
+// general kinds the kernels run with a diagonal of ones (`1.0 * v` is exact) and every preconditioned vector is replaced
+// by `apply_slot`'s result right after the kernel that produced it; inner products with it are re-formed by a separate
+// stream kernel.
 enum MkPreconKind {
     MK_PRECON_NONE = 0,
-    MK_PRECON_DIAG,        // mk_solver_set_precon_diag: the borrowed diagonal is d_prec itself
-    MK_PRECON_HOST,        // mk_solver_set_precon_callback: `fn(user, in, out)` on the host, through pinned buffers
-    MK_PRECON_CSR,         // mk_solver_set_precon_csr: a device matrix or composite `op` (counted in op->dependents), e.g. the
-                           // inverted diagonal blocks of block-Jacobi; the product stays in HBM
-    MK_PRECON_OBJECT       // mk_solver_set_precon_ilu / _lbfgs: a held MkDeviceOp `obj`, applied in place
+    MK_PRECON_DIAG,        // mk_solver_set_precon_diag / _lls_precon: the borrowed diagonal is d_prec (d_dm, d_dn) itself
+    MK_PRECON_HOST,        // mk_solver_set_precon_callback / _lls_precon_callback: `fn(user, in, out)` on the host, through
+                           // pinned buffers
+    MK_PRECON_CSR,         // mk_solver_set_precon_csr / _lls_precon_csr: a device matrix or composite `op` (counted in
+                           // op->dependents), e.g. the inverted diagonal blocks of block-Jacobi; the product stays in HBM
+    MK_PRECON_OBJECT       // mk_solver_set_precon_ilu / _lbfgs, mk_solver_set_lls_precon_ilu / _bfgs: a held MkDeviceOp `obj`
 };
 
 struct MkPrecon {
@@ -70,6 +72,9 @@ struct MkPrecon {
     void *user = nullptr;
     const mk_csr *op = nullptr;
     const MkDeviceOp *obj = nullptr;
+    bool general() const { return kind >= MK_PRECON_HOST; }
+    void hold() const;              // take the reference a slot keeps on a device matrix or object
+    void release();                 // drop it and go back to MK_PRECON_NONE
 };
 
 struct mk_solver {
@@ -78,15 +83,24 @@ struct mk_solver {
     MkPrecon precon;
     const double *d_prec = nullptr; // what the kernels multiply by: the diagonal (n entries), d_ones for a general kind, or null
     double *d_ones = nullptr;       // (owned, allocated with the first general preconditioner)
-    double *h_pin = nullptr, *h_pout = nullptr;   // pinned staging of the host callback
+    double *h_pin = nullptr, *h_pout = nullptr;   // pinned staging of the host callback (least squares: max(m, n) entries)
     double *d_ptmp = nullptr;       // product target when a site preconditions a vector in place by a device matrix
     int *d_nohalt = nullptr;        // two zero words: the halt input of a kernel that must run after the loop has ended
-    bool general_precon() const { return precon.kind >= MK_PRECON_HOST; }
+    bool general_precon() const { return precon.general(); }
     // `next` (a general kind) replaces whatever is attached; the messages name the entry point `who`, and for an object what
     // it is (`noun`, `plural`)
     int attach_precon(const MkPrecon &next, const char *who, const char *noun = nullptr, const char *plural = nullptr);
     void clear_precon();            // back to MK_PRECON_NONE: the only place a preconditioner's reference is released
-    int apply_precon(const double *in_dev, double *out_dev, bool force = false);   // out = precon * in ; unless `force`, a no-op once the loop has halted
+    int apply_precon(const double *in_dev, double *out_dev, bool force = false) {   // out = precon * in ; unless `force`, a no-op once the loop has halted
+        return apply_slot(precon, n, in_dev, out_dev, force);
+    }
+    // out = slot * in for a general kind on vectors of `len` entries: the square solvers' `precon` and the two slots of the
+    // least-squares solvers (mk_lls.hip).  `need_pos` (least squares, beta of lsqr.py:258): a device scalar that must be
+    // > 0 for a HOST callback to run, read with the halt word in the one synchronisation; the launches of the device kinds
+    // cannot be gated from the host -- their caller gates the product itself (mk_apply_csr_slot) or takes an out-of-place
+    // result on the device
+    int apply_slot(const MkPrecon &slot, int64_t len, const double *in_dev, double *out_dev, bool force,
+                   const double *need_pos = nullptr);
     mk_params prm{};
     int64_t n = 0;        // local rows = length of every solver vector
     int64_t nx = 0;       // length of vectors that feed an SpMV (n + halo)
@@ -162,8 +176,12 @@ mk_solver *mk_make_tfqmr();
 mk_solver *mk_make_minres();
 mk_solver *mk_make_symmlq();
 mk_solver *mk_make_lls(int kind);
-int mk_lls_set_metric(mk_solver *s, const double *dm, const double *dn);
-int mk_lls_set_callbacks(mk_solver *s, mk_precon_fn fn_m, void *user_m, mk_precon_fn fn_n, void *user_n);
+// M (side 0, nrows(A) entries) or N (side 1, ncols(A) entries) of a least-squares solver: `next` replaces what the side
+// held (MK_PRECON_NONE removes it; MK_PRECON_DIAG comes with the borrowed diagonal `diag`); the other side is untouched
+int mk_lls_set_side(mk_solver *s, int side, const MkPrecon &next, const double *diag, const char *who, const char *noun);
+int mk_lls_side_kind(const mk_solver *s, int side);          // the MkPreconKind that side holds
+// ... a device object (F null: none) on behalf of the entry points that live with the objects' types
+int mk_lls_set_precon_object(mk_solver *s, int side, const MkDeviceOp *F, const char *who, const char *noun);
 
 #ifdef __HIPCC__
 // ------------------------------------------------------------------ small shared kernels
@@ -289,6 +307,26 @@ static inline int mk_launch_spmv_on(mk_solver *s, const mk_csr *M, const double 
                                     const Gate &gate = Gate()) {
     mk_spmv_launch_blocks(M, mk_grid_spmv_for(M), s->stream, x, epi, gate, [&] { return s->next_halt(); }, s->d_part);
     return MK_OK;
+}
+
+// out = op * in by the device matrix of a preconditioner slot (mk_solver::apply_slot's MK_PRECON_CSR case).  Like every kernel
+// of the loop the product obeys the halt words: once the loop condition has failed it is a no-op, exactly when the reference
+// applies nothing more -- unless `force` (set-up).  `gate` is MkNoGate for every site but N of the least-squares loops,
+// whose product runs under the A' product's own gate (mk_lls.hip, GateV).
+template <class Gate>
+static inline int mk_apply_csr_slot(mk_solver *s, const mk_csr *op, int64_t len, const double *in_dev, double *out_dev,
+                                    bool force, const Gate &gate) {
+    double *dst = (in_dev == out_dev) ? s->d_ptmp : out_dev;
+    const int grid = mk_grid_spmv_for(op);
+    if (force) {
+        mk_spmv_launch_blocks(op, grid, s->stream, in_dev, MkPlainEpi{dst}, gate,
+                              [&] { return MkHalt{s->d_nohalt, 0, 0}; }, s->d_part);
+        if (dst != out_dev) MK_HIP(hipMemcpyAsync(out_dev, dst, sizeof(double) * (size_t)len, hipMemcpyDeviceToDevice, s->stream));
+    } else {
+        mk_spmv_launch_blocks(op, grid, s->stream, in_dev, MkPlainEpi{dst}, gate, [&] { return s->next_halt(); }, s->d_part);
+        if (dst != out_dev) mk_launch_stream(s, MkOpCopy{dst, out_dev}, len);
+    }
+    return mk_ctx().pending_rc;
 }
 
 template <class Epi, class Gate = MkNoGate>

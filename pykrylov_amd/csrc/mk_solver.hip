@@ -35,53 +35,52 @@ int mk_solver::init_common(const mk_csr *A_, const mk_params *p) {
     return MK_OK;
 }
 
-int mk_solver::apply_precon(const double *in_dev, double *out_dev, bool force) {
-    switch (precon.kind) {
+int mk_solver::apply_slot(const MkPrecon &slot, int64_t len, const double *in_dev, double *out_dev, bool force,
+                          const double *need_pos) {
+    switch (slot.kind) {
         case MK_PRECON_OBJECT: {
             // out = P in by the object's own launches (the factor's sweeps, the chain of the two-loop recursion); each obeys
             // the halt words like the product below
-            const int rc = force ? precon.obj->enqueue(in_dev, out_dev, stream, nullptr, nullptr)
-                                 : precon.obj->enqueue(in_dev, out_dev, stream, d_halt, &q);
+            const int rc = force ? slot.obj->enqueue(in_dev, out_dev, stream, nullptr, nullptr)
+                                 : slot.obj->enqueue(in_dev, out_dev, stream, d_halt, &q);
             return rc != MK_OK ? rc : mk_ctx().pending_rc;
         }
-        case MK_PRECON_CSR: {
-            // out = op * in on the device.  Like every kernel of the loop the product obeys the halt words: once the loop
-            // condition has failed it is a no-op, exactly when the reference applies nothing more -- unless `force`.
-            double *dst = (in_dev == out_dev) ? d_ptmp : out_dev;
-            const int grid = mk_grid_spmv_for(precon.op);
-            if (force) {
-                mk_spmv_launch_blocks(precon.op, grid, stream, in_dev, MkPlainEpi{dst}, MkNoGate(),
-                                      [&] { return MkHalt{d_nohalt, 0, 0}; }, d_part);
-                if (dst != out_dev) MK_HIP(hipMemcpyAsync(out_dev, dst, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-            } else {
-                mk_spmv_launch_blocks(precon.op, grid, stream, in_dev, MkPlainEpi{dst}, MkNoGate(),
-                                      [&] { return next_halt(); }, d_part);
-                if (dst != out_dev) mk_launch_stream(this, MkOpCopy{dst, out_dev}, n);
-            }
-            return mk_ctx().pending_rc;
-        }
+        case MK_PRECON_CSR:                                  // out = op * in on the device
+            return mk_apply_csr_slot(this, slot.op, len, in_dev, out_dev, force, MkNoGate());
         case MK_PRECON_HOST: {
             int h = 0;
+            double pos = 1.0;
             MK_HIP(hipMemcpyAsync(&h, d_halt + (q & 1), sizeof(int), hipMemcpyDeviceToHost, stream));   // the next kernel's word
-            if (n > 0) MK_HIP(hipMemcpyAsync(h_pin, in_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, stream));
+            if (need_pos) MK_HIP(hipMemcpyAsync(&pos, need_pos, sizeof(double), hipMemcpyDeviceToHost, stream));
+            if (len > 0) MK_HIP(hipMemcpyAsync(h_pin, in_dev, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, stream));
             MK_HIP(hipStreamSynchronize(stream));
             if (h && !force) return MK_OK;                   // the loop has ended: the reference applies nothing more
-            if (precon.fn(precon.user, h_pin, h_pout) != 0) {
+            if (!(pos > 0)) return MK_OK;                    // ... or does not reach this site (lsqr.py:258)
+            if (slot.fn(slot.user, h_pin, h_pout) != 0) {
                 const int rc = mk_fail(MK_ERR_STATE, "the host preconditioner callback reported a failure");
                 if (mk_ctx().pending_rc == MK_OK) mk_ctx().pending_rc = rc;
                 return rc;
             }
-            if (n > 0) MK_HIP(hipMemcpyAsync(out_dev, h_pout, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, stream));
+            if (len > 0) MK_HIP(hipMemcpyAsync(out_dev, h_pout, sizeof(double) * (size_t)len, hipMemcpyHostToDevice, stream));
             return MK_OK;
         }
         default: return MK_OK;                               // (a diagonal acts inside the kernels)
     }
 }
 
+void MkPrecon::hold() const {
+    if (kind == MK_PRECON_CSR) op->dependents += 1;
+    if (kind == MK_PRECON_OBJECT) obj->hold();
+}
+
+void MkPrecon::release() {
+    if (kind == MK_PRECON_CSR) mk_release_operand(op);
+    if (kind == MK_PRECON_OBJECT) obj->release();
+    *this = MkPrecon{};
+}
+
 void mk_solver::clear_precon() {
-    if (precon.kind == MK_PRECON_CSR) mk_release_operand(precon.op);
-    if (precon.kind == MK_PRECON_OBJECT) precon.obj->release();
-    precon = MkPrecon{};
+    precon.release();
     d_prec = nullptr;
 }
 
@@ -390,8 +389,7 @@ int mk_solver::attach_precon(const MkPrecon &next, const char *who, const char *
     }
     if (next.kind == MK_PRECON_CSR && !d_ptmp) MK_HIP(hipMalloc((void **)&d_ptmp, sizeof(double) * len + 16));
     // take the new reference first, then drop the old one: re-setting the attached object must not free it
-    if (next.kind == MK_PRECON_CSR) next.op->dependents += 1;
-    if (next.kind == MK_PRECON_OBJECT) next.obj->hold();
+    next.hold();
     clear_precon();
     precon = next;
     d_prec = d_ones;
@@ -417,7 +415,7 @@ extern "C" int mk_solver_set_precon_csr(mk_solver *s, const mk_csr *M) {
     return s->attach_precon(p, "mk_solver_set_precon_csr");
 }
 
-// (the entry points of the objects, mk_solver_set_precon_ilu / _lbfgs, live with their types in mk_ilu.hip / mk_lbfgs.hip)
+// (the entry points of the objects, mk_solver_set_precon_ilu / _bfgs, live with their types in mk_ilu.hip / mk_lbfgs.hip)
 int mk_set_precon_object(mk_solver *s, const MkDeviceOp *F, const char *who, const char *noun, const char *plural) {
     MK_ARG(s);
     if (!F) return s->clear_precon(), MK_OK;
@@ -427,20 +425,69 @@ int mk_set_precon_object(mk_solver *s, const MkDeviceOp *F, const char *who, con
     return s->attach_precon(p, who, noun, plural);
 }
 
+static bool mk_is_lls(const mk_solver *s) { return s->prm.kind >= MK_LSQR && s->prm.kind <= MK_CRAIGMR; }
+
+// The two-sided setters: a side that is given something takes it in place of what it held; a side that is given NULL
+// loses what THIS setter attaches (a diagonal here, a callback below) and keeps anything else.
 extern "C" int mk_solver_set_lls_precon(mk_solver *s, const double *diag_m, const double *diag_n) {
     MK_ARG(s);
     MK_ARG(MK_ALIGNED16(diag_m) && MK_ALIGNED16(diag_n));
-    if (s->prm.kind < MK_LSQR || s->prm.kind > MK_CRAIGMR)
-        return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_set_lls_precon: not a least-squares solver");
-    return mk_lls_set_metric(s, diag_m, diag_n);
+    if (!mk_is_lls(s)) return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_set_lls_precon: not a least-squares solver");
+    const double *diag[2] = {diag_m, diag_n};
+    for (int side = 0; side < 2; ++side) {
+        MkPrecon p;
+        if (diag[side]) p.kind = MK_PRECON_DIAG;
+        else if (mk_lls_side_kind(s, side) != MK_PRECON_DIAG) continue;
+        const int rc = mk_lls_set_side(s, side, p, diag[side], "mk_solver_set_lls_precon", nullptr);
+        if (rc != MK_OK) return rc;
+    }
+    return MK_OK;
 }
 
 extern "C" int mk_solver_set_lls_precon_callback(mk_solver *s, mk_precon_fn fn_m, void *user_m, mk_precon_fn fn_n,
                                                  void *user_n) {
     MK_ARG(s);
-    if (s->prm.kind < MK_LSQR || s->prm.kind > MK_CRAIGMR)
-        return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_set_lls_precon_callback: not a least-squares solver");
-    return mk_lls_set_callbacks(s, fn_m, user_m, fn_n, user_n);
+    if (!mk_is_lls(s)) return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_set_lls_precon_callback: not a least-squares solver");
+    const mk_precon_fn fn[2] = {fn_m, fn_n};
+    void *const user[2] = {user_m, user_n};
+    for (int side = 0; side < 2; ++side) {
+        MkPrecon p;
+        if (fn[side]) {
+            p.kind = MK_PRECON_HOST;
+            p.fn = fn[side];
+            p.user = user[side];
+        } else if (mk_lls_side_kind(s, side) != MK_PRECON_HOST) {
+            continue;
+        }
+        const int rc = mk_lls_set_side(s, side, p, nullptr, "mk_solver_set_lls_precon_callback", nullptr);
+        if (rc != MK_OK) return rc;
+    }
+    return MK_OK;
+}
+
+extern "C" int mk_solver_set_lls_precon_csr(mk_solver *s, int side, const mk_csr *P) {
+    MK_ARG(s);
+    MK_ARG(side == MK_LLS_SIDE_M || side == MK_LLS_SIDE_N);
+    if (!mk_is_lls(s)) return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_set_lls_precon_csr: not a least-squares solver");
+    MkPrecon p;
+    if (P) {
+        p.kind = MK_PRECON_CSR;
+        p.op = P;
+    }
+    return mk_lls_set_side(s, side, p, nullptr, "mk_solver_set_lls_precon_csr", nullptr);
+}
+
+// (the entry points of the objects, mk_solver_set_lls_precon_ilu / _bfgs, live with their types in mk_ilu.hip / mk_lbfgs.hip)
+int mk_lls_set_precon_object(mk_solver *s, int side, const MkDeviceOp *F, const char *who, const char *noun) {
+    MK_ARG(s);
+    MK_ARG(side == MK_LLS_SIDE_M || side == MK_LLS_SIDE_N);
+    if (!mk_is_lls(s)) return mk_fail(MK_ERR_UNSUPPORTED, "%s: not a least-squares solver", who);
+    MkPrecon p;
+    if (F) {
+        p.kind = MK_PRECON_OBJECT;
+        p.obj = F;
+    }
+    return mk_lls_set_side(s, side, p, nullptr, who, noun);
 }
 
 extern "C" int mk_solver_destroy(mk_solver *s) {

@@ -29,6 +29,7 @@ class _LlsBase(KrylovMethod):
         self.normal_eqns_resids = []
         self.dir_errors_window = []
         self.iterates = []
+        self.precon_route = {'M': 'none', 'N': 'none'}       # how the last solve applied M and N (see _lls_precon)
         self.msg = ['The exact solution is  x = 0                              ',
                     'Ax - b is small enough, given atol, btol                  ',
                     'The least-squares solution is good enough, given atol     ',
@@ -45,19 +46,43 @@ class _LlsBase(KrylovMethod):
         d = self.dir_errors_window
         return float(d[-1]) * float(np.sqrt(res.aux[3])) if len(d) and np.isfinite(d[-1]) else 0.0
 
-    def _lls_diag(self, P, size, which):
-        """M / N for the device loop: the fp64 diagonal of an operator that exposes one (DiagonalOperator,
-        linop.py:473-516; applied inside the kernels), else the callable itself -- the reference applies them as
-        functions, `u = M(Mu)` (lsqr.py:190) -- to be called back on the host at those sites."""
+    def _lls_precon(self, P, size, which):
+        """How the device loop applies M / N (`u = M(Mu)`, `v = N(Nv)`: lsqr.py:190,202,254,266), resolved like
+        ``KrylovMethod._device_precon`` resolves ``precon``; returns ``(route, payload)`` with the route in the words of
+        ``DeviceRun.precon_kind``:
+
+        * ``'diag'``: an operator that exposes its diagonal (DiagonalOperator, linop.py:473-516) -- the fp64 array, applied
+          inside the kernels;
+        * ``'ilu'`` / ``'lbfgs'``: an incomplete factorization (`tools.ilu0` / `tools.ic0`) or an inverse L-BFGS operator,
+          applied on the device by its sweeps / two-loop chain;
+        * ``'device'``: a CsrOperator, or an operator with a device view (`tools.block_jacobi`, block operators of device
+          matrices), square and of that side's size -- a product on the device;
+        * ``'host'``: any other callable, called back on the host at those sites."""
         if P is None:
-            return None
+            return 'none', None
+        name = self.__class__.__name__
         diag = getattr(P, 'diag', None)
-        if diag is None or callable(diag):
-            if not callable(P) and not hasattr(P, '__mul__'):
-                raise TypeError('%s: %s must be callable (the reference evaluates `%s(vector)`); got a %s'
-                                % (self.__class__.__name__, which, which, type(P).__name__))
-            return P
-        return as_f64_vector(diag, size, which + '.diag')
+        if diag is not None and not callable(diag):
+            return 'diag', as_f64_vector(diag, size, which + '.diag')
+        from ..tools import IluPreconditioner
+        from ..lbfgs import InverseLBFGSOperator
+        from ..linop import CsrOperator
+        is_ilu = isinstance(P, IluPreconditioner)
+        if is_ilu or (isinstance(P, InverseLBFGSOperator) and P._is_inverse):
+            if tuple(P.shape) != (size, size):
+                raise ValueError('%s: %s has shape %s, expected %s' % (name, which, tuple(P.shape), (size, size)))
+            return ('ilu' if is_ilu else 'lbfgs'), P
+        dev = P if isinstance(P, CsrOperator) else None
+        if dev is None and hasattr(P, '_device_view'):
+            dev = P._device_view()
+        if dev is not None and getattr(dev, 'local_size', None) is None:
+            if tuple(dev.shape) != (size, size):
+                raise ValueError('%s: %s has shape %s, expected %s' % (name, which, tuple(dev.shape), (size, size)))
+            return 'device', dev
+        if not callable(P) and not hasattr(P, '__mul__'):
+            raise TypeError('%s: %s must be callable (the reference evaluates `%s(vector)`); got a %s'
+                            % (name, which, which, type(P).__name__))
+        return 'host', P
 
     @staticmethod
     def _host_thunk(P, size, errors):
@@ -76,10 +101,9 @@ class _LlsBase(KrylovMethod):
 
     def _run(self, rhs, itnlim, damp, atol, btol, conlim, M, N, kwargs, x_rows=False):
         A = self._device_operator()
-        # M and N: the reference calls them as functions, `u = M(Mu)`, `v = N(Nv)` (lsqr.py:190,202); on the device
-        # path they must be diagonal (an operator with a `.diag` array: DiagonalOperator, linop.py:473-516)
-        dm = self._lls_diag(M, A.shape[0], 'M')
-        dn = self._lls_diag(N, A.shape[1], 'N')
+        # M and N: the reference calls them as functions, `u = M(Mu)`, `v = N(Nv)` (lsqr.py:190,202)
+        sides = (self._lls_precon(M, A.shape[0], 'M'), self._lls_precon(N, A.shape[1], 'N'))
+        self.precon_route = {'M': sides[0][0], 'N': sides[1][0]}
         if kwargs.get('wantvar', False):
             raise NotImplementedError('wantvar is broken in the reference as well (lsqr.py:155)')
         m, n = A.shape
@@ -101,18 +125,25 @@ class _LlsBase(KrylovMethod):
         handle = ctypes.c_void_p()
         _lib.check(lib.mk_solver_create(A.handle, ctypes.byref(p), ctypes.byref(handle)))
         cb_errors = []
-        cb_m = self._host_thunk(dm, m, cb_errors) if (dm is not None and not isinstance(dm, np.ndarray)) else None
-        cb_n = self._host_thunk(dn, n, cb_errors) if (dn is not None and not isinstance(dn, np.ndarray)) else None
-        d_dm = _lib.DeviceArray.from_numpy(dm) if isinstance(dm, np.ndarray) else None
-        d_dn = _lib.DeviceArray.from_numpy(dn) if isinstance(dn, np.ndarray) else None
+        cbs = [self._host_thunk(P, size, cb_errors) if route == 'host' else None
+               for (route, P), size in zip(sides, (m, n))]
+        d_diag = [_lib.DeviceArray.from_numpy(P) if route == 'diag' else None for route, P in sides]
         try:
             _lib.check(lib.mk_solver_set_transpose(handle, At.handle))
-            if cb_m is not None or cb_n is not None:
+            if cbs[0] is not None or cbs[1] is not None:
                 none = ctypes.cast(None, _lib.PRECON_FN)
-                _lib.check(lib.mk_solver_set_lls_precon_callback(handle, cb_m or none, None, cb_n or none, None))
-            if d_dm is not None or d_dn is not None:
-                _lib.check(lib.mk_solver_set_lls_precon(handle, None if d_dm is None else d_dm.ptr,
-                                                        None if d_dn is None else d_dn.ptr))
+                _lib.check(lib.mk_solver_set_lls_precon_callback(handle, cbs[0] or none, None, cbs[1] or none, None))
+            if d_diag[0] is not None or d_diag[1] is not None:
+                _lib.check(lib.mk_solver_set_lls_precon(handle, None if d_diag[0] is None else d_diag[0].ptr,
+                                                        None if d_diag[1] is None else d_diag[1].ptr))
+            for side, (route, P) in enumerate(sides):       # (the solver holds what it is given until it is destroyed)
+                if route == 'device':
+                    _lib.check(lib.mk_solver_set_lls_precon_csr(handle, side, P.handle))
+                elif route == 'ilu':
+                    _lib.check(lib.mk_solver_set_lls_precon_ilu(handle, side, P._live()))
+                elif route == 'lbfgs':
+                    _lib.check(lib.mk_solver_set_lls_precon_bfgs(handle, side, P._live()))
+
             def chk(rc):
                 if rc != 0 and hasattr(A, 'raise_pending'):
                     A.raise_pending()                         # what a matrix-free operator raised in its callback
@@ -163,7 +194,7 @@ class _LlsBase(KrylovMethod):
         finally:
             lib.mk_solver_destroy(handle)
             d_rhs.free()
-            for buf in (d_dm, d_dn):
+            for buf in d_diag:
                 if buf is not None:
                     buf.free()
         itn = int(res.itn)
