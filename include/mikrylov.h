@@ -524,11 +524,48 @@ MK_API int mk_lbfgs_download(const mk_lbfgs *F, double *s_host, double *y_host);
  * solver's operator carries an exchange plan), MK_ERR_ARG on a size mismatch.  Call before mk_solver_setup.  A pair stored
  * between two solves is seen by the next one. */
 MK_API int mk_solver_set_precon_lbfgs(mk_solver *s, const mk_lbfgs *F);
+/* Chebyshev polynomial preconditioner z = p_k(A) r of a square, SYMMETRIC device matrix A (the caller vouches for the
+ * symmetry): the Chebyshev iteration for A z = r from z = 0 on an interval [lmin, lmax], 0 < lmin < lmax, that should hold
+ * A's spectrum (Saad, Iterative Methods, Alg. 12.1); with scale_diag != 0 the iteration for D^-1 A z = D^-1 r, D = diag(A).
+ * 1 <= degree <= MK_CHEB_MAX_DEGREE.  lmax <= 0 on input takes the Gershgorin bound max_r sum_j |a_rj| (scaled: / |a_rr|),
+ * computed on the device, each row added left to right in stored order; lmin <= 0 takes lmax / 30 (the convention of hypre
+ * and Ifpack2 where no lower estimate is given).  The coefficients depend on lmin, lmax and degree only and are computed
+ * once on the host, one rounding per operation:
+ *     theta = 0.5*(lmax+lmin);  delta = 0.5*(lmax-lmin);  sigma = theta/delta;  c0 = 1.0/theta;  rho_0 = 1.0/sigma
+ *     j = 1..k:  rho_j = 1.0/(2.0*sigma - rho_{j-1});  c1_j = rho_j*rho_{j-1};  c2_j = (2.0*rho_j)/delta
+ * The object borrows A (A may be destroyed meanwhile: it lives on until the object goes) and owns three vectors of nrows
+ * doubles, and 1 / a_rr when scaled.  MK_ERR_ARG for a non-square matrix, a degree out of range, non-finite bounds, an
+ * interval without 0 < lmin < lmax, and -- with scale_diag -- a row that stores no diagonal entry or a zero one (the message
+ * names the smallest such row).  MK_ERR_UNSUPPORTED for operators that hold no arrays of their own and for operators with an
+ * exchange plan. */
+typedef struct mk_cheb mk_cheb;
+#define MK_CHEB_MAX_DEGREE 64
+MK_API int mk_cheb_create(const mk_csr *A, int32_t degree, double lmin, double lmax, int32_t scale_diag, mk_cheb **out);
+/* Destroying an object that solvers still hold (mk_solver_set_precon_cheb) is deferred until the last of them goes. */
+MK_API int mk_cheb_destroy(mk_cheb *F);
+/* out = p_k(A) in on device vectors (in == out allowed; out of place, `in` is not modified): one stream launch
+ *     res = in (scaled: dinv * in);  d_0 = res * c0;  out = d_0
+ * then per step j = 1..k one product of A on d_{j-1}, in the storage format A has, whose row epilogue does, in this order,
+ *     s = row sum (scaled: s = dinv_r * s);  rv = res_r - s;  d_j = c1_j * d_{j-1,r} + c2_j * rv;  out_r = out_r + d_j;  res_r = rv
+ * with one rounding per operation.  Enqueued on the library's stream. */
+MK_API int mk_cheb_apply(const mk_cheb *F, const double *in_dev, double *out_dev);
+/* info[k] for k < min(cap, MK_CHEB_INFO_LEN): 0 rows, 1 degree, 2 scaled, 3 launches per apply (1 + degree; a storage format
+ * that cuts a product into several launches adds its own), 4 device bytes held, 5 set-up time (us), 6 / 7 whether lmin / lmax
+ * is the default. */
+#define MK_CHEB_INFO_LEN 8
+MK_API int mk_cheb_info(const mk_cheb *F, int64_t *info, int32_t cap);
+/* 3 + 2 * degree doubles to the host: lmin and lmax as used, c0, then c1_1, c2_1, ..., c1_k, c2_k. */
+MK_API int mk_cheb_coefficients(const mk_cheb *F, double *host);
+/* ... and as the preconditioner of the six square solvers, like mk_solver_set_precon_ilu: applied on the device at the
+ * sites of the callback, every launch obeying the loop's halt words; the solver holds a reference until it is destroyed or
+ * the preconditioner is replaced; NULL removes it.  Single GPU, MK_ERR_ARG on a size mismatch.  Call before
+ * mk_solver_setup. */
+MK_API int mk_solver_set_precon_cheb(mk_solver *s, const mk_cheb *F);
 /* The least-squares kinds take two preconditioners, applied by the reference as `u = M(Mu)` in the m-space and
  * `v = N(Nv)` in the n-space of the Golub-Kahan process (lls/lsqr.py:189-190,201-202,253-254,265-266 and the same
  * lines of lsmr.py, craig.py, craigmr.py).  Each side holds ONE preconditioner of any of the kinds the square solvers
  * take -- a diagonal, a host callback, a device matrix or composite, an incomplete factorization, an inverse L-BFGS
- * operator -- and every setter below replaces what its side held (releasing the reference it kept on a matrix or object)
+ * operator, a Chebyshev polynomial preconditioner -- and every setter below replaces what its side held (releasing the reference it kept on a matrix or object)
  * without touching the other side.  MK_ERR_UNSUPPORTED for the six square solvers.  Call before mk_solver_setup.
  *
  * Diagonals: device arrays with the diagonals of M (nrows(A) entries) and N (ncols(A) entries), multiplied inside the
@@ -550,6 +587,7 @@ MK_API int mk_solver_set_lls_precon_callback(mk_solver *s, mk_precon_fn fn_m, vo
  *   _bfgs:  an inverse L-BFGS operator (mk_lbfgs) of that side's size; a pair stored between two solves is seen by the
  *           next one.  (Spelt _bfgs on purpose: the names that contain "lbfgs" are the operator's own entry points and the
  *           square solvers' mk_solver_set_precon_lbfgs, a closed set that tests/test_lbfgs_cpu.py pins name by name.)
+ *   _cheb:  a Chebyshev polynomial preconditioner (mk_cheb_create) of a symmetric matrix of that side's size.
  * The solver holds a factor or operator until it is destroyed or the side is given something else: destroying the object
  * meanwhile is deferred.  NULL removes what the side holds.  MK_ERR_ARG on a size mismatch or a non-square matrix.
  * Single GPU: with row blocks over several GPUs (mk_csr_set_row_block) only diagonals are supported, mk_solver_setup fails
@@ -558,6 +596,7 @@ enum { MK_LLS_SIDE_M = 0, MK_LLS_SIDE_N = 1 };
 MK_API int mk_solver_set_lls_precon_csr(mk_solver *s, int side, const mk_csr *P);
 MK_API int mk_solver_set_lls_precon_ilu(mk_solver *s, int side, const mk_ilu *F);
 MK_API int mk_solver_set_lls_precon_bfgs(mk_solver *s, int side, const mk_lbfgs *F);
+MK_API int mk_solver_set_lls_precon_cheb(mk_solver *s, int side, const mk_cheb *F);
 /* Everything before the `while` loop of the reference's solve().  rhs_dev has n_local
  * entries; guess_dev may be NULL (x0 = 0).  Neither is modified. */
 MK_API int mk_solver_setup(mk_solver *s, const double *rhs_dev, const double *guess_dev);

@@ -35,6 +35,8 @@ class MkRowOp(ctypes.Structure):
 
 MK_ILU_INFO_LEN = 12      # entries of mk_ilu_info (include/mikrylov.h)
 MK_LBFGS_INFO_LEN = 12    # entries of mk_lbfgs_info
+MK_CHEB_INFO_LEN = 8      # entries of mk_cheb_info
+MK_CHEB_MAX_DEGREE = 64   # highest degree of mk_cheb_create
 
 MK_ROW_SCALE, MK_ROW_ADD, MK_ROW_SUB, MK_ROW_RSUB, MK_ROWPROG_MAX = 1, 2, 3, 4, 4
 
@@ -149,11 +151,18 @@ PROTOTYPES = {
     "mk_lbfgs_info": (ctypes.c_int, [c_vp, P(c_i64), c_i32]),
     "mk_lbfgs_download": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mk_solver_set_precon_lbfgs": (ctypes.c_int, [c_vp, c_vp]),
+    "mk_cheb_create": (ctypes.c_int, [c_vp, c_i32, c_f64, c_f64, c_i32, P(c_vp)]),
+    "mk_cheb_destroy": (ctypes.c_int, [c_vp]),
+    "mk_cheb_apply": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mk_cheb_info": (ctypes.c_int, [c_vp, P(c_i64), c_i32]),
+    "mk_cheb_coefficients": (ctypes.c_int, [c_vp, P(c_f64)]),
+    "mk_solver_set_precon_cheb": (ctypes.c_int, [c_vp, c_vp]),
     "mk_solver_set_lls_precon_callback": (ctypes.c_int, [c_vp, PRECON_FN, c_vp, PRECON_FN, c_vp]),
     "mk_solver_set_lls_precon": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mk_solver_set_lls_precon_csr": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
     "mk_solver_set_lls_precon_ilu": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
     "mk_solver_set_lls_precon_bfgs": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
+    "mk_solver_set_lls_precon_cheb": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
     "mk_solver_setup": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mk_solver_iterate": (ctypes.c_int, [c_vp, c_i64, P(c_i64)]),
     "mk_solver_finish": (ctypes.c_int, [c_vp, P(MkResult)]),

@@ -115,6 +115,17 @@ class KrylovMethod(object):
                 raise ValueError('%s: precon has shape %s, expected %s'
                                  % (self.__class__.__name__, precon.shape, (self.op.shape[0], self.op.shape[0])))
             return precon
+        # * a Chebyshev polynomial preconditioner (`tools.chebyshev`) is applied ON the device: one product of its matrix per
+        #   step, the step's vector updates fused into the product's row epilogue
+        from .tools import ChebyshevPreconditioner
+        if isinstance(precon, ChebyshevPreconditioner):
+            if getattr(self.op, 'local_size', None) is not None:
+                raise NotImplementedError('%s: Chebyshev preconditioners are single-GPU; the operator is row-partitioned'
+                                          % self.__class__.__name__)
+            if precon.shape != (self.op.shape[0], self.op.shape[0]):
+                raise ValueError('%s: precon has shape %s, expected %s'
+                                 % (self.__class__.__name__, precon.shape, (self.op.shape[0], self.op.shape[0])))
+            return precon
         # * a device matrix (CsrOperator -- e.g. the inverted diagonal blocks of `tools.block_jacobi`) or a block
         #   operator of device matrices is applied ON the device, as a product at the same sites
         from .linop import CsrOperator
@@ -222,10 +233,12 @@ class DeviceRun(object):
         diagonal the DeviceArray, which `close` frees unless it is the caller's) and the call that attaches it to a solver
         handle (the constructor's, and every placement draw's)."""
         lib = self.lib
-        from .tools import IluPreconditioner
+        from .tools import ChebyshevPreconditioner, IluPreconditioner
         from .lbfgs import InverseLBFGSOperator
         if precon is None:
             return 'none', None, lambda handle: 0
+        if isinstance(precon, ChebyshevPreconditioner):
+            return 'cheb', precon, lambda handle: lib.mk_solver_set_precon_cheb(handle, precon._live())
         if isinstance(precon, IluPreconditioner):
             return 'ilu', precon, lambda handle: lib.mk_solver_set_precon_ilu(handle, precon._live())
         if isinstance(precon, InverseLBFGSOperator) and precon._is_inverse:

@@ -55,6 +55,8 @@ class _LlsBase(KrylovMethod):
           inside the kernels;
         * ``'ilu'`` / ``'lbfgs'``: an incomplete factorization (`tools.ilu0` / `tools.ic0`) or an inverse L-BFGS operator,
           applied on the device by its sweeps / two-loop chain;
+        * ``'cheb'``: a Chebyshev polynomial preconditioner (`tools.chebyshev`) of a symmetric matrix of that side's size,
+          applied on the device by its chain of products;
         * ``'device'``: a CsrOperator, or an operator with a device view (`tools.block_jacobi`, block operators of device
           matrices), square and of that side's size -- a product on the device;
         * ``'host'``: any other callable, called back on the host at those sites."""
@@ -64,9 +66,13 @@ class _LlsBase(KrylovMethod):
         diag = getattr(P, 'diag', None)
         if diag is not None and not callable(diag):
             return 'diag', as_f64_vector(diag, size, which + '.diag')
-        from ..tools import IluPreconditioner
+        from ..tools import ChebyshevPreconditioner, IluPreconditioner
         from ..lbfgs import InverseLBFGSOperator
         from ..linop import CsrOperator
+        if isinstance(P, ChebyshevPreconditioner):
+            if tuple(P.shape) != (size, size):
+                raise ValueError('%s: %s has shape %s, expected %s' % (name, which, tuple(P.shape), (size, size)))
+            return 'cheb', P
         is_ilu = isinstance(P, IluPreconditioner)
         if is_ilu or (isinstance(P, InverseLBFGSOperator) and P._is_inverse):
             if tuple(P.shape) != (size, size):
@@ -141,6 +147,8 @@ class _LlsBase(KrylovMethod):
                     _lib.check(lib.mk_solver_set_lls_precon_csr(handle, side, P.handle))
                 elif route == 'ilu':
                     _lib.check(lib.mk_solver_set_lls_precon_ilu(handle, side, P._live()))
+                elif route == 'cheb':
+                    _lib.check(lib.mk_solver_set_lls_precon_cheb(handle, side, P._live()))
                 elif route == 'lbfgs':
                     _lib.check(lib.mk_solver_set_lls_precon_bfgs(handle, side, P._live()))
 

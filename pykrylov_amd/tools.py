@@ -248,3 +248,144 @@ class IluPreconditioner(LinearOperator):
     def __del__(self):
         self.free()
 
+
+
+def _cheb_operator(op):
+    """Kind / shape checks of `chebyshev`, made before the device is touched (those of ``_ilu_operator(symmetric=True)``)."""
+    what = 'chebyshev'
+    shape = getattr(op, 'shape', None)
+    if shape is None or len(shape) != 2:
+        raise TypeError('%s needs an operator with a `.shape`; got %r' % (what, type(op).__name__))
+    from .linop import CsrOperator
+    if getattr(op, 'local_size', None) is not None:
+        raise NotImplementedError('%s: the operator is row-partitioned; the Chebyshev preconditioner is single-GPU' % what)
+    if not isinstance(op, CsrOperator):
+        raise TypeError('%s: %r holds no CSR arrays on the device; form its matrix (e.g. `to_csr_arrays()` of a device '
+                        'operator) and wrap it in a CsrOperator' % (what, type(op).__name__))
+    if shape[0] != shape[1]:
+        raise ValueError('%s needs a square operator, got shape %s' % (what, (shape,)))
+    if not getattr(op, 'symmetric', False):
+        raise ValueError('%s needs a symmetric operator (declared with symmetric=True)' % what)
+    return op
+
+
+def chebyshev(op, degree=4, lmin=None, lmax=None, ratio=30.0, scale_diag=False):
+    """Chebyshev polynomial preconditioner ``z = p_k(A) r`` of a symmetric device matrix (a :class:`CsrOperator` declared
+    ``symmetric=True``) as a DEVICE preconditioner: `degree` = k steps of the Chebyshev iteration for ``A z = r`` from
+    ``z = 0`` on the interval ``[lmin, lmax]`` (Saad, Alg. 12.1), each step ONE product of `op` in the storage format it has,
+    with the step's vector updates fused into the product's row epilogue -- no triangular solve, no level schedule.
+
+    `lmax` defaults to the Gershgorin bound of the matrix (computed on the device), `lmin` to ``lmax / ratio`` (30: the
+    convention of hypre and Ifpack2 where no lower estimate is given).  ``scale_diag=True`` runs the iteration on
+    ``D^-1 A`` (Jacobi scaling; every row must store a nonzero diagonal, MkError naming the row otherwise) -- the operator is
+    then symmetric in the D inner product only.  ``1 <= degree <= 64``.  Passed as ``precon=`` to BiCGSTAB / CGS / TFQMR /
+    MINRES / SYMMLQ, or as ``M=`` / ``N=`` to the least-squares solvers, it is applied without a host round trip."""
+    _cheb_operator(op)
+    if isinstance(degree, bool) or not isinstance(degree, (int, np.integer)):
+        raise ValueError('chebyshev: degree must be an integer from 1 to %d, got %r' % (_lib.MK_CHEB_MAX_DEGREE, degree))
+    if not 1 <= int(degree) <= _lib.MK_CHEB_MAX_DEGREE:
+        raise ValueError('chebyshev: degree must be an integer from 1 to %d, got %r' % (_lib.MK_CHEB_MAX_DEGREE, degree))
+    for name, v in (('lmin', lmin), ('lmax', lmax)):
+        if v is not None and not (np.isfinite(v) and v > 0):
+            raise ValueError('chebyshev: %s must be positive and finite, got %r' % (name, v))
+    if lmin is not None and lmax is not None and not lmin < lmax:
+        raise ValueError('chebyshev: the interval needs 0 < lmin < lmax, got lmin = %r, lmax = %r' % (lmin, lmax))
+    if lmin is None and not (np.isfinite(ratio) and ratio > 1):
+        raise ValueError('chebyshev: ratio must be finite and > 1, got %r' % (ratio,))
+    return ChebyshevPreconditioner(op, int(degree), lmin, lmax, float(ratio), bool(scale_diag))
+
+
+class ChebyshevPreconditioner(LinearOperator):
+    """``p_k(A)`` of a symmetric device matrix, resident in HBM (`chebyshev`).  ``self * v`` applies it to a NumPy vector,
+    `apply_device` to DeviceArray vectors; solvers given it as ``precon=`` (``M=`` / ``N=``) apply it on the device
+    (mk_solver_set_precon_cheb / mk_solver_set_lls_precon_cheb).  Attributes: `degree`, `interval` (``(lmin, lmax)`` as
+    used), `coefficients` (``c0`` and the arrays ``c1``, ``c2`` of the steps), `scaled`, `info` (mk_cheb_info as a dict).
+    `free()` releases this object's reference; a solver that still applies the object keeps it alive."""
+
+    def __init__(self, op, degree, lmin, lmax, ratio, scale_diag):
+        lib = _lib.init()
+        self._lib = lib
+        self._handle = None
+        self._buf = None
+        self._n = int(op.shape[0])
+        self.degree = int(degree)
+        self.scaled = bool(scale_diag)
+        if lmin is None and lmax is not None:
+            lmin = float(lmax) / ratio
+        elif lmin is None and ratio != 30.0:
+            # lmin = (default lmax) / ratio: the Gershgorin bound first, from an object of degree 1
+            probe = self._create(op, 1, 0.0, 0.0)
+            try:
+                lmin = self._coefficients(probe, 1)[1] / ratio
+            finally:
+                lib.mk_cheb_destroy(probe)
+        self._handle = self._create(op, self.degree, 0.0 if lmin is None else float(lmin), 0.0 if lmax is None else float(lmax))
+        self._op = op                      # (keeps the matrix's Python owner alive beside the library's own count)
+        LinearOperator.__init__(self, self._n, self._n, matvec=self._apply, symmetric=True, dtype=np.float64)
+
+    def _create(self, op, degree, lmin, lmax):
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.mk_cheb_create(op.handle, degree, lmin, lmax, int(self.scaled), ctypes.byref(h)))
+        return h.value
+
+    def _coefficients(self, handle, degree):
+        v = (ctypes.c_double * (3 + 2 * degree))()
+        _lib.check(self._lib.mk_cheb_coefficients(handle, v))
+        return np.array(v[:], dtype=np.float64)
+
+    handle = property(lambda self: self._live(), doc="Opaque ``mk_cheb*`` for libmikrylov.")
+
+    @property
+    def info(self):
+        names = ('rows', 'degree', 'scaled', 'launches', 'bytes', 'setup_us', 'lmin_default', 'lmax_default')
+        v = (ctypes.c_int64 * _lib.MK_CHEB_INFO_LEN)()
+        _lib.check(self._lib.mk_cheb_info(self._live(), v, _lib.MK_CHEB_INFO_LEN))
+        return dict(zip(names, (int(x) for x in v)))
+
+    @property
+    def interval(self):
+        "``(lmin, lmax)`` as used."
+        c = self._coefficients(self._live(), self.degree)
+        return float(c[0]), float(c[1])
+
+    @property
+    def coefficients(self):
+        "``(c0, c1, c2)``: the scalar of the first direction and the two coefficient arrays of the steps 1 .. degree."
+        c = self._coefficients(self._live(), self.degree)
+        return float(c[2]), c[3::2].copy(), c[4::2].copy()
+
+    def _live(self):
+        if not self._handle:
+            raise ValueError('the Chebyshev preconditioner has been freed')
+        return self._handle
+
+    def _apply(self, r):
+        h = self._live()
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if self._buf is None:
+            self._buf = _lib.DeviceArray(self._n, zero=False)
+        self._buf.upload(r)
+        _lib.check(self._lib.mk_cheb_apply(h, self._buf.ptr, self._buf.ptr))
+        return self._buf.to_numpy()
+
+    def apply_device(self, d_in, d_out):
+        "``d_out = p_k(A) d_in`` on DeviceArray vectors (`d_in is d_out` allowed); enqueued on the library's stream."
+        for d in (d_in, d_out):
+            if not isinstance(d, _lib.DeviceArray) or d.n != self._n or d.dtype != np.float64 or not d.ptr:
+                raise ValueError('apply_device needs live float64 DeviceArray vectors of %d entries' % self._n)
+        _lib.check(self._lib.mk_cheb_apply(self._live(), d_in.ptr, d_out.ptr))
+
+    def free(self):
+        if getattr(self, '_buf', None) is not None:
+            self._buf.free()
+            self._buf = None
+        if getattr(self, '_handle', None):
+            try:
+                self._lib.mk_cheb_destroy(self._handle)
+            except Exception:
+                pass
+            self._handle = None
+        self._op = None
+
+    def __del__(self):
+        self.free()
