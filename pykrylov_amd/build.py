@@ -50,7 +50,7 @@ def _newer(target, deps):
 
 def build(force=False, verbose=False, tag=None, defines=()):
     """`tag` / `defines`: an experiment build beside the product -- libmikrylov_<tag>.so compiled with -D<define> ...,
-    loaded instead of the product when MIKRYLOV_LIB points at it (tools/variants.sh)."""
+    loaded instead of the product when MIKRYLOV_LIB points at it."""
     global OUT, OBJDIR
     if tag:
         OUT = os.path.join(HERE, "libmikrylov_%s.so" % tag)

@@ -75,16 +75,14 @@ using CgSpmvEpi = CgSpmvEpiT<false>;
 
 // K1f: the brick march's "fuse" hooks (mk_spmv_fmt9.h).  Only ever launched on a plain march matrix (formats 9 / 10 / 11):
 // MARCH_ONLY keeps the generic launcher from compiling any other kernel for them.
-#ifndef MK_FUSE_NT_DEF
-#define MK_FUSE_NT_DEF 7                                     // 1 nt loads of x, 2 nt stores of x, 4 nt stores of the new p (profiles/r05_fuse_nt_ab.txt: all three)
-#endif
+constexpr int MK_FUSE_NT_ALL = 7;                            // 1 nt loads of x, 2 nt stores of x, 4 nt stores of the new p (profiles/r05_fuse_nt_ab.txt: all three)
 template <bool NTY, bool FX = true>
 struct CgFusedEpiT {
     static constexpr int NACC = 1, SLOT0 = 0;
     static constexpr bool SYM_MARCH = true;
     static constexpr bool FUSE_X = FX;                       // false: x stays out of the kernel (deferred, cg_xapply)
     static constexpr bool MARCH_ONLY = true;                 // only the march kernels are compiled for it (mk_device.h)
-    static constexpr int FUSE_NT = NTY ? MK_FUSE_NT_DEF : 0;  // vectors beyond the Infinity Cache: x / the new p past the caches too
+    static constexpr int FUSE_NT = NTY ? MK_FUSE_NT_ALL : 0;  // vectors beyond the Infinity Cache: x / the new p past the caches too
     double *Ap;
     const double *fuse_r;
     double *fuse_x, *fuse_p, *fuse_dump;
@@ -385,16 +383,15 @@ struct CgSolver : mk_solver {
     }
 
     static bool want_fuse() {
-        const char *e = getenv("MK_CG_FUSE");              // (read at every setup: tests switch it between solves)
-        return !e || atoi(e) != 0;
+        return mk_switch_int<MK_SW_CG_FUSE>() != 0;        // (read at every setup: tests switch it between solves)
     }
     // MK_CG_XDEFER = m (read at every setup like MK_CG_FUSE).  Unset: 8 where the vectors lie beyond the Infinity Cache -- the
     // deferral saves HBM traffic and costs one kernel boundary per m passes, so a problem whose x stays in the cache has
     // nothing to gain from it -- and 1 elsewhere.
     int want_xdefer() const {
-        const char *e = getenv("MK_CG_XDEFER");
-        int m = e ? atoi(e) : (sizeof(double) * (size_t)n > ((size_t)256 << 20) ? 8 : 1);
-        return m < 1 ? 1 : (m > MK_XD_MAX ? MK_XD_MAX : m);
+        static_assert(mk_switch_table[MK_SW_CG_XDEFER].hi == MK_XD_MAX, "the ring holds at most MK_XD_MAX + 1 directions");
+        const MkSwitchVal m = mk_switch<MK_SW_CG_XDEFER>();
+        return m.set ? (int)m.v : (sizeof(double) * (size_t)n > ((size_t)256 << 20) ? 8 : 1);
     }
     // grow the ring towards m + 1 buffers; returns the m it can serve (0: not even the pair of today's fused pass).  The buffers
     // beyond the pair may take an eighth of the device memory that is free: a placement search holds several solvers at once.

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(MK_BLOCK) void classify_tiles_kernel(int64_t nrows,
 // interior / boundary tile lists and the second stream (halo mode with a non-empty halo)
 int build_overlap_plan(mk_csr *A) {
     MkExchange &ex = A->ex;
-    if (getenv("MK_NO_OVERLAP") || A->ntiles < 2 || ex.n_halo == 0) return MK_OK;
+    if (A->ntiles < 2 || ex.n_halo == 0) return MK_OK;
     hipStream_t st = mk_ctx().stream;
     int *d_flags = nullptr;
     MK_HIP(hipMalloc((void **)&d_flags, sizeof(int) * (size_t)A->ntiles));
@@ -232,7 +232,7 @@ extern "C" int mk_comm_init(int nranks, int rank, const void *id128) {
     g_nranks = nranks;
     g_rank = rank;
     g_comm_halo = nullptr;
-    if (nranks > 1 && g_rccl.CommSplit && !getenv("MK_SHARED_COMM")) {
+    if (nranks > 1 && g_rccl.CommSplit) {
         ncclComm_t c2 = nullptr;
         if (g_rccl.CommSplit(g_comm, 0, rank, &c2, nullptr) == ncclSuccess && c2) g_comm_halo = c2;
     }

@@ -28,23 +28,9 @@ int mk_fail(int code, const char *fmt, ...) {
 
 static int *g_halt0 = nullptr;   // two zero ints: "never halted" flags for standalone kernels
 
-static int env_cap(const char *name, int dflt) {
-    const char *v = getenv(name);
-    int c = v ? atoi(v) : dflt;
-    if (c < 1) c = 1;
-    return c > MK_MAXP ? MK_MAXP : c;
-}
-// (MK_GRID_DYNAMIC: read the overrides at every call -- grid sweeps inside one process, tools/grid_sweep.py)
-int mk_cap_stream() {
-    static const bool dyn = getenv("MK_GRID_DYNAMIC") != nullptr;
-    static int c = env_cap("MK_GRID_STREAM", 512);
-    return dyn ? env_cap("MK_GRID_STREAM", 512) : c;
-}
-int mk_cap_spmv() {
-    static const bool dyn = getenv("MK_GRID_DYNAMIC") != nullptr;
-    static int c = env_cap("MK_GRID_SPMV", 1024);
-    return dyn ? env_cap("MK_GRID_SPMV", 1024) : c;
-}
+static_assert(mk_switch_table[MK_SW_GRID_STREAM].hi == MK_MAXP && mk_switch_table[MK_SW_GRID_SPMV].hi == MK_MAXP, "grid caps <= MK_MAXP");
+int mk_cap_stream() { return (int)mk_switch_int<MK_SW_GRID_STREAM>(); }
+int mk_cap_spmv() { return (int)mk_switch_int<MK_SW_GRID_SPMV>(); }
 
 extern "C" int mk_version(void) { return MK_VERSION; }
 
@@ -146,9 +132,8 @@ MkStager g_stager;
 
 int stager_threads() {
     if (g_stager.n >= 0) return g_stager.n;
-    const char *e = getenv("MK_COPY_THREADS");
-    int want = e ? atoi(e) : 4;
-    want = want < 0 ? 0 : (want > MK_COPY_MAXT ? MK_COPY_MAXT : want);
+    static_assert(mk_switch_table[MK_SW_COPY_THREADS].hi == MK_COPY_MAXT, "one pinned buffer and stream per worker");
+    const int want = (int)mk_switch_int<MK_SW_COPY_THREADS>();
     int got = 0;
     for (; got < want; ++got) {
         if (hipHostMalloc(&g_stager.pin[got], MK_COPY_PIECE, hipHostMallocDefault) != hipSuccess) break;

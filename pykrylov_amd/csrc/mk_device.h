@@ -124,19 +124,13 @@ double *mk_pen_dump();                           // mk_format.hip: the dump rows
 // stripe length (tiles, a power of two) of tile order 3; 0 = the matrix does not use it
 static inline const mk_csr *mk_owner(const mk_csr *A) { return A->base ? A->base : A; }
 static inline int mk_tile_stripe(const mk_csr *A) {
-    static const char *env = getenv("MK_SPMV_STRIPE");
-    int s = mk_owner(A)->want_stripe > 0 ? mk_owner(A)->want_stripe : (env ? atoi(env) : 0);
-    if (s <= 0) s = 32;
+    const int s = mk_owner(A)->want_stripe > 0 ? mk_owner(A)->want_stripe : 32;
     int p2 = 1;
     while (2 * p2 <= s) p2 *= 2;
     return p2;
 }
 // plane period (tiles) of tile order 4
-static inline int mk_tile_plane(const mk_csr *A) {
-    static const char *env = getenv("MK_SPMV_PLANE");
-    if (mk_owner(A)->want_plane > 0) return mk_owner(A)->want_plane;
-    return env ? atoi(env) : 0;
-}
+static inline int mk_tile_plane(const mk_csr *A) { return mk_owner(A)->want_plane > 0 ? mk_owner(A)->want_plane : 0; }
 // order 4 needs whole planes and whole strips per XCD
 static inline bool mk_tile_map4_ok(const mk_csr *A) {
     const int P = mk_tile_plane(A), S = mk_tile_stripe(A);
@@ -150,9 +144,8 @@ static inline bool mk_tile_map4_ok(const mk_csr *A) {
 // and the caches hold a good part of the pass's working set) the 27-point product gains 5 % and the CG pass LOSES
 // 3-7 %, with the stores, the loads or both: off there.
 static inline int mk_stream_nt(const mk_csr *A) {
-    static const char *env = getenv("MK_SPMV_NT");
     if (mk_owner(A)->want_nt >= 0) return mk_owner(A)->want_nt;
-    if (env) return atoi(env);
+    if (mk_switch<MK_SW_SPMV_NT>().set) return (int)mk_switch_int<MK_SW_SPMV_NT>();
     return (!A->comp_kind && !A->host_fn && 8 * A->nrows > (int64_t)256 * 1024 * 1024) ? 1 : 0;
 }
 static inline int mk_store_nt(const mk_csr *A) { return mk_stream_nt(A); }
@@ -160,9 +153,8 @@ static inline int mk_tile_map(const mk_csr *A) {
     if (A->comp_kind >= 4) return 0;
     if (A->comp_kind) return mk_tile_map(A->comp_kind == 3 ? A->comp_a : A->comp_b);
     if (A->host_fn) return 0;
-    static const char *env = getenv("MK_SPMV_MAP");
-    if (mk_owner(A)->want_map >= 0 || env) {
-        int m = mk_owner(A)->want_map >= 0 ? mk_owner(A)->want_map : atoi(env);
+    if (mk_owner(A)->want_map >= 0) {
+        int m = mk_owner(A)->want_map;
         if (m == 4 && !mk_tile_map4_ok(A)) m = 2;
         return m;
     }
@@ -189,7 +181,7 @@ static inline int mk_grid_spmv_for(const mk_csr *A) {
     if (A->comp_kind >= 4) return mk_grid_spmv(A->ntiles);   // (the final launch walks the accumulated rows)
     if (A->comp_kind) return mk_grid_spmv_for(A->comp_kind == 3 ? A->comp_a : A->comp_b);   // the final launch's matrix
     int g = mk_grid_spmv(A->ntiles);
-    if (getenv("MK_GRID_SPMV") || A->host_fn) return g;
+    if (mk_switch<MK_SW_GRID_SPMV>().set || A->host_fn) return g;
     const MkPlan *P = mk_csr_plan(A);
     int64_t cap = mk_cap_spmv();
     if (P && P->cblocks.size() >= 2 && P->cblocks[0]->plan.fmt == 3 && A->ex.mode < 0) {   // column blocks as resident tiles
@@ -346,10 +338,6 @@ static inline bool mk_pen_split(const MkPlan *P, int *za, int *zb, bool thin = f
     *za = lo;
     *zb = hi_s;
     return true;
-}
-static inline bool mk_pen_tail_gen() {                      // (MK_PEN_TAIL_GEN=0: round 5's split of a slab -- six + leftover boundary planes -- for A/B runs)
-    static const char *env = getenv("MK_PEN_TAIL_GEN");
-    return !env || atoi(env) != 0;
 }
 static inline int mk_pen_items(const MkCsrView &v) {
     const int n1 = (v.pen_zb - v.pen_za + v.pen_zc - 1) / v.pen_zc, n2 = (v.pen_yb - v.pen_ya + v.pen_zc - 1) / v.pen_zc;

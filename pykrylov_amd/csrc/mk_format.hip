@@ -514,36 +514,24 @@ void plan_free(MkPlan &P) {
     P = MkPlan();
 }
 
-int default_format() {
-    static int f = [] {
-        const char *e = getenv("MK_SPMV_FORMAT");
-        int v = e ? atoi(e) : 11;
-        return v < 0 ? 0 : (v > 11 ? 11 : v);
-    }();
-    return f;
-}
+int default_format() { return (int)mk_switch_int<MK_SW_SPMV_FORMAT>(); }
 
 // Column-block size in bytes of x (0: off, the default -- see cblocks_build)
 int64_t colblock_bytes(const mk_csr *A) {
-    static int64_t env = [] {
-        const char *e = getenv("MK_COLBLOCK_KB");
-        return e ? atoll(e) * 1024 : (int64_t)0;
-    }();
-    static const bool env_set = getenv("MK_COLBLOCK_KB") != nullptr;
-    if (A->want_cb_kb < 0 && !env_set) {
+    const MkSwitchVal env = mk_switch<MK_SW_COLBLOCK_KB>();
+    if (A->want_cb_kb < 0 && !env.set) {
         // AUTOMATIC (round 4): long rows gathered from an x several times the chip's L2 capacity -- the transposed operator
         // of a tall least-squares problem (lls/lsqr.py:264: 1e6 rows of ~20 entries over 4e6 columns, x = 32 MB) pulls a
         // 64-byte sector through the fabric for nearly every nonzero on the gather path (350 us per product), and its
         // tiles are too long for the resident-tile format.  In 4 MiB column blocks the same product takes 232 us (LSQR
-        // 1 665 -> 2 050 passes per second, gpurun_out of tools/r04_cb.sh): with ~20 entries per row the 24 B per row and
+        // 1 665 -> 2 050 passes per second, tools/r04_cb.sh at commit e1780bd): with ~20 entries per row the 24 B per row and
         // block of carried sums are small beside the sectors saved.  (5 entries per row: slower, see cblocks_build.)
         const int64_t xbytes = 8 * A->x_len();
         const bool long_rows = A->nrows > 0 && A->nnz >= 12 * A->nrows;
         if (long_rows && xbytes >= ((int64_t)16 << 20) && A->ex.mode < 0) return -((int64_t)8 << 20);   // (negative: automatic)
         return 0;
     }
-    const int64_t b = A->want_cb_kb >= 0 ? (int64_t)A->want_cb_kb * 1024 : env;
-    return b < 0 ? 0 : b;
+    return (A->want_cb_kb >= 0 ? (int64_t)A->want_cb_kb : (int64_t)env.v) * 1024;
 }
 static void cblocks_drop(MkPlan &P) {
     for (mk_csr *B : P.cblocks) mk_csr_destroy(B);
@@ -623,41 +611,36 @@ int cblocks_build(const mk_csr *A, int64_t blk_override = 0) {
     // its launch takes the resident-tile kernel of format 3 with ONE phase -- the tile's (column, value) stream by DMA into LDS,
     // lane t walks row t with a cursor, running sums in from / out to the carry vector -- instead of the gather path's two
     // staged passes per 2 048 nonzeros: the lls `A' u` product 231 -> measured in DESIGN.md 3.1-6.  All blocks or none (one grid).
-    static const char *ecb = getenv("MK_CB_RESIDENT");
-    if (!ecb || atoi(ecb) > 0) {
-        bool all = true;
-        for (size_t bi = 0; bi < P.cblocks.size(); ++bi) {
-            mk_csr *B = P.cblocks[bi];
-            plan_free(B->plan);
-            B->plan.built = true;
-            if (resident_plan(B, B->plan, true) != MK_OK || B->plan.fmt != 3) all = false;
-            hipFree(B->plan.d_carry);                        // (a block never runs as a stepped pair product)
-            B->plan.d_carry = nullptr;
-            // phases over the block's OWN slice of x (bw columns from b * bw), 1.5 MiB each: a slice larger than an L2's share
-            // is walked in lockstep like a whole format-3 matrix
-            const int64_t c0 = (int64_t)bi * bw;
-            int64_t kk = (8 * bw + RT_SLICE_BYTES - 1) / RT_SLICE_BYTES;
-            static const char *ecp = getenv("MK_CB_PHASES");
-            if (ecp && atoi(ecp) > 0) kk = atoi(ecp);
-            kk = kk < 1 ? 1 : (kk > 64 ? 64 : kk);
-            B->plan.rt_k = (int)kk;
-            B->plan.rt_w = (int)((bw + kk - 1) / kk);
-            B->plan.rt_c0 = (int)c0;
-            B->plan.rt_reg = 0;
-        }
-        if (!all && automatic) {
-            // a tile of some block is too long for LDS: smaller blocks once, if they still are at most CB_MAX; otherwise the
-            // matrix keeps its single launch (blocks on the gather path were measured slower than that: DESIGN.md 3.1-4)
-            cblocks_drop(P);
-            if (blk > ((int64_t)4 << 20) && (xbytes + blk / 2 - 1) / (blk / 2) <= CB_MAX) return cblocks_build(A, -(blk / 2));
-            return MK_OK;
-        }
-        if (!all)
-            for (mk_csr *B : P.cblocks) {
-                plan_free(B->plan);                          // (no leak of what resident_plan allocated)
-                B->plan.built = true;
-            }
+    bool all = true;
+    for (size_t bi = 0; bi < P.cblocks.size(); ++bi) {
+        mk_csr *B = P.cblocks[bi];
+        plan_free(B->plan);
+        B->plan.built = true;
+        if (resident_plan(B, B->plan, true) != MK_OK || B->plan.fmt != 3) all = false;
+        hipFree(B->plan.d_carry);                            // (a block never runs as a stepped pair product)
+        B->plan.d_carry = nullptr;
+        // phases over the block's OWN slice of x (bw columns from b * bw), 1.5 MiB each: a slice larger than an L2's share
+        // is walked in lockstep like a whole format-3 matrix
+        const int64_t c0 = (int64_t)bi * bw;
+        int64_t kk = (8 * bw + RT_SLICE_BYTES - 1) / RT_SLICE_BYTES;
+        kk = kk < 1 ? 1 : (kk > 64 ? 64 : kk);
+        B->plan.rt_k = (int)kk;
+        B->plan.rt_w = (int)((bw + kk - 1) / kk);
+        B->plan.rt_c0 = (int)c0;
+        B->plan.rt_reg = 0;
     }
+    if (!all && automatic) {
+        // a tile of some block is too long for LDS: smaller blocks once, if they still are at most CB_MAX; otherwise the
+        // matrix keeps its single launch (blocks on the gather path were measured slower than that: DESIGN.md 3.1-4)
+        cblocks_drop(P);
+        if (blk > ((int64_t)4 << 20) && (xbytes + blk / 2 - 1) / (blk / 2) <= CB_MAX) return cblocks_build(A, -(blk / 2));
+        return MK_OK;
+    }
+    if (!all)
+        for (mk_csr *B : P.cblocks) {
+            plan_free(B->plan);                              // (no leak of what resident_plan allocated)
+            B->plan.built = true;
+        }
     return MK_OK;
 }
 
@@ -688,7 +671,7 @@ __global__ __launch_bounds__(MK_BLOCK) void tile_extent_kernel(const int32_t *__
 constexpr int RT_CAP_MAX = 2560;                             // 30 KB of LDS per workgroup
 int resident_plan(const mk_csr *A, MkPlan &P, bool forced) {
     const int64_t xbytes = 8 * A->x_len();
-    if (!forced && (xbytes <= 5 * (1 << 20) || getenv("MK_NO_RESIDENT"))) return MK_OK;   // (crossover measured at 650 k rows x 5)
+    if (!forced && xbytes <= 5 * (1 << 20)) return MK_OK;   // (crossover measured at 650 k rows x 5)
     if (A->ex.mode >= 0 && !forced) return MK_OK;            // (partitioned matrices: their x slices are short already)
     hipStream_t st = mk_ctx().stream;
     int *d_max = nullptr, h_mm[2] = {0, 0};
@@ -704,22 +687,17 @@ int resident_plan(const mk_csr *A, MkPlan &P, bool forced) {
     if (!ok || h_max < 1) return MK_OK;
     const int cap = (h_max + 255) / 256 * 256;
     if (cap > RT_CAP_MAX) return MK_OK;                      // long rows: the chunked gather path
-    // short rows and more tiles than resident workgroups: pairs of tiles, the second one in registers (mk_spmv_fmt3r.h).
-    // MK_RT_REG=0 keeps one tile per step (A/B measurements).
+    // short rows and more tiles than resident workgroups: pairs of tiles, the second one in registers (mk_spmv_fmt3r.h)
     P.max_row = h_mm[1];
-    static const char *ereg = getenv("MK_RT_REG");
-    const int allow = ereg ? atoi(ereg) : 1;
-    const int rt_reg = (allow >= 1 && h_mm[1] <= 5 && A->ntiles > MK_MAXP && 8 * A->x_len() < ((int64_t)1 << 31)) ? 1 : 0;
-    static const char *estep = getenv("MK_RT_STEPPED");
-    const bool stepped = rt_reg && A->ntiles > 2 * (int64_t)MK_MAXP && (!estep || atoi(estep) > 0);
+    const int rt_reg = (h_mm[1] <= 5 && A->ntiles > MK_MAXP && 8 * A->x_len() < ((int64_t)1 << 31)) ? 1 : 0;
+    const bool stepped = rt_reg && A->ntiles > 2 * (int64_t)MK_MAXP;
     // column phases (speed only: a row's sum runs in column order whatever the phases).  Round 5 sweep (profiles/
     // r05_scattered_phase_sweep.txt): a product of ONE step per workgroup is fastest with slices of about 1 MiB (config 3: 8 - 9
     // phases, +1 % over the 6 of 1.5 MiB), a product of MANY steps with slices of 0.6 MiB (the 4e6-row `A v`: 12 - 16 phases,
     // LSQR +7 %): two neighbouring slices then share an L2 and workgroups a phase apart still hit it
     const int64_t slice = stepped ? (int64_t)640 << 10 : (int64_t)1 << 20;   // (column blocks set their own phases: cblocks_build)
     int64_t k = (xbytes + slice - 1) / slice;
-    static const char *env = getenv("MK_RT_PHASES");
-    if (env && atoi(env) > 0) k = atoi(env);
+    if (mk_switch_int<MK_SW_RT_PHASES>() > 0) k = mk_switch_int<MK_SW_RT_PHASES>();
     k = k < 1 ? 1 : (k > 64 ? 64 : k);
     P.fmt = 3;
     P.rt_cap = cap;
@@ -800,7 +778,6 @@ bool sell_build(const mk_csr *A, MkPlan &P, int ds, bool with_slots) {
 // the matrix in fmt 2.  `raw`: fmt 1 -> fmt 5, the same for a matrix without a value dictionary -- patterns of the bare
 // slots, and the values copied into tile-sliced ELL order (any failure, or more than 12.5 % of padding: stays fmt 1).
 bool pattern_plan(const mk_csr *A, MkPlan &P, bool raw) {
-    if (getenv("MK_NO_PATTERNS")) return false;
     const uint32_t *words = raw ? nullptr : P.d_pk;
     const int cmax = P.wide ? MK_WCHUNKS_WIDE : MK_WCHUNKS_MAX;
     const int cap_words = P.wide ? PAT_WORDS_WIDE : PAT_WORDS;
@@ -812,7 +789,7 @@ bool pattern_plan(const mk_csr *A, MkPlan &P, bool raw) {
     uint32_t *d_pat = nullptr;
     const char *why = "";
     auto cleanup = [&]() {
-        if (*why && getenv("MK_DEBUG_PLAN")) fprintf(stderr, "mikrylov: no row patterns (%s)\n", why);
+        if (*why && mk_switch_flag<MK_SW_DEBUG_PLAN>()) fprintf(stderr, "mikrylov: no row patterns (%s)\n", why);
         hipFree(d_state);
         hipFree(d_table);
         hipFree(d_keys);
@@ -908,7 +885,7 @@ bool pattern_plan(const mk_csr *A, MkPlan &P, bool raw) {
     P.npat = count;
     P.pmax = pmax;
     P.fmt = P.wide ? (raw ? 7 : 8) : (raw ? 5 : 4);
-    if (getenv("MK_DEBUG_PLAN")) fprintf(stderr, "mikrylov: %lld rows, %d row patterns of <= %d entries (fmt %d)\n", (long long)A->nrows, count, pmax, P.fmt);
+    if (mk_switch_flag<MK_SW_DEBUG_PLAN>()) fprintf(stderr, "mikrylov: %lld rows, %d row patterns of <= %d entries (fmt %d)\n", (long long)A->nrows, count, pmax, P.fmt);
     // the per-nonzero streams are not read any more (tiles without windows gather from the CSR arrays)
     hipFree(P.d_pk);
     hipFree(P.d_slots);
@@ -1202,13 +1179,7 @@ __global__ __launch_bounds__(MK_BLOCK) void pen_sym_pack(int64_t nrows, int64_t 
 
 // Below this many rows the windowed pattern format (fmt 4) keeps the matrix: a brick march needs a few thousand
 // (brick, chunk) items of >= 8 planes to fill the chip, and a cache-resident product is latency bound either way
-int64_t pencil_min_rows() {
-    static int64_t v = [] {
-        const char *e = getenv("MK_PENCIL_MIN_ROWS");
-        return e ? atoll(e) : (int64_t)1 << 21;
-    }();
-    return v;
-}
+int64_t pencil_min_rows() { return mk_switch_int<MK_SW_PENCIL_MIN_ROWS>(); }
 
 // true: P holds format 9.  false: the matrix is not of the class (P untouched apart from freed scratch).
 // bricks per line, brick rows per plane (the last brick of a line / the last group of four lines may be partly empty)
@@ -1224,22 +1195,20 @@ void pencil_geometry(const mk_csr *A, MkPlan &P, int64_t L, int64_t PP) {
     P.pen_ny = (int)((PP + L - 1) / L);
     P.pen_bx = (int)pen_bx_of(L);
     P.pen_bpp = (int)(pen_bx_of(L) * pen_by_of(L, PP));
-    static const char *env_gen = getenv("MK_PEN_GEN");       // (1: the general-geometry kernels on aligned geometries too, A/B runs)
-    P.pen_gen = (!pen_aligned(L, PP) || (env_gen && atoi(env_gen) == 1)) ? 2 : 0;
+    // (MK_PEN_GEN=1: the general-geometry kernels on aligned geometries too, A/B runs)
+    P.pen_gen = (!pen_aligned(L, PP) || mk_switch_int<MK_SW_PEN_GEN>() == 1) ? 2 : 0;
     // XCD-contiguous deal: an eighth of the plane's bricks per XCD; on a general geometry ceil(bpp / 8) with empty item slots
     // behind the last brick, from 64 bricks per plane on (below that the empty slots would idle whole XCDs)
     P.pen_per = (P.pen_bpp % 8 == 0) ? P.pen_bpp / 8 : ((P.pen_gen && P.pen_bpp >= 64) ? (P.pen_bpp + 7) / 8 : 0);
     P.pen_xlo = A->loc_lo ? A->nrows : -1;                   // a slab: where the neighbours' planes sit in the input vector
     P.pen_xhi = A->loc_hi ? A->nrows + A->loc_lo : -1;
     // chunks: the kernel keeps two workgroups per CU resident (its register ring), so 512 (brick, chunk) items fill the
-    // chip in one round; more chunks only add pipeline fills and re-read two planes per chunk start (512^3, tools/
-    // r05_pencil_variants.sh: 4 chunks of 132 planes 441 us, 8 of 66 436, one of 516 421).  At least 6 planes per chunk, a
+    // chip in one round; more chunks only add pipeline fills and re-read two planes per chunk start (512^3, profiles/
+    // r05_pencil_variants.txt: 4 chunks of 132 planes 441 us, 8 of 66 436, one of 516 421).  At least 6 planes per chunk, a
     // multiple of the ring depth so that only the matrix's last chunk has planes left over.
-    static const char *env_zc = getenv("MK_PENCIL_ZC");
     int chunks = (512 + P.pen_bpp - 1) / P.pen_bpp;
     int zc = (P.pen_nz + chunks - 1) / chunks;
     zc = zc < MK_PEN_R ? MK_PEN_R : zc;
-    if (env_zc && atoi(env_zc) > 0) zc = atoi(env_zc);
     zc = (zc + MK_PEN_R - 1) / MK_PEN_R * MK_PEN_R;
     P.pen_zc = zc;
     P.pen_chunks = (P.pen_nz + zc - 1) / zc;
@@ -1283,7 +1252,7 @@ bool pencil_plan(const mk_csr *A, MkPlan &P, bool forced, int want) {
     if (h_stats[2] > 7 || L <= 1 || PP < L) return drop();
     const bool two_d = (L == PP);
     if (L == PP) {
-        // (measured, tools/r06_march_sizes.py: CG on 2000^2 16.8 k passes per second on either format, on 4000^2 3.86 k on the
+        // (measured, tools/r06_march_sizes.py at commit e1780bd: CG on 2000^2 16.8 k passes per second on either format, on 4000^2 3.86 k on the
         //  windowed format 4 against 4.22 k marched: chosen automatically from four times the 3-D threshold on)
         if (!forced && A->nrows < 4 * pencil_min_rows()) return drop();
         L = 128;
@@ -1291,7 +1260,7 @@ bool pencil_plan(const mk_csr *A, MkPlan &P, bool forced, int want) {
     if (L >= PP || A->nrows % PP != 0 || A->nrows / PP < 2 || pen_bx_of(L) * pen_by_of(L, PP) > (1 << 24)) return drop();
     // partly empty bricks: at least half of the lanes must have rows (L = 132, 9 lines: 39 %; L = 37: 29 %)
     if (!pen_aligned(L, PP) && 2 * PP < 512 * pen_bx_of(L) * pen_by_of(L, PP)) return drop();
-    // ... and chosen AUTOMATICALLY only where the march wins (tools/r06_march_sizes.py, profiles/r06_march_sizes.txt: CG passes
+    // ... and chosen AUTOMATICALLY only where the march wins (profiles/r06_march_sizes.txt: CG passes
     // per second, windowed -> march): bricks at least 90 % full from the usual 2^21 rows on (250^3 2 901 -> 3 931, 500^3 430 -> 584),
     // bricks 78 % full (L = 200, 300, 400) only from 2^24 rows on (200^3, 8 M rows: 7 828 -> 6 506; 300^3 1 982 -> 2 220; 400^3
     // 884 -> 939)
@@ -1504,7 +1473,7 @@ void mk_csr_plan_reset(const mk_csr *A) {
 // The brick march is a per-MATRIX format, but whether it pays depends on the LOOP: CG's product epilogue (and a plain
 // product's) loads nothing, so the march's software pipeline runs undisturbed (512^3: CG 442 -> 582 passes per second);
 // the other loops' epilogues load their vectors inside the pipelined loop and every such load waits for everything issued
-// before it (512^3: MINRES 369 -> 292, SYMMLQ 357 -> 270, BiCGSTAB 254 -> 229; tools/r05_solvers_on_bricks.py).  So the
+// before it (512^3: MINRES 369 -> 292, SYMMLQ 357 -> 270, BiCGSTAB 254 -> 229; tools/r05_solvers_on_bricks.py at commit e1780bd).  So the
 // solver being created says what it is, and an automatically chosen format follows the last one -- unless other solvers
 // are alive on the matrix (their partial-sum counts were sized for the format in use) or the caller fixed the format.
 // a solver was created on (+1) / removed from (-1) A: counted on A's owner and on every matrix a composite borrows

@@ -321,10 +321,8 @@ static int mk_ilu_create(const mk_csr *A, int kind, mk_ilu **out) {
     F->kind = kind;
     F->n = n;
     F->nnz = nnz;
-    {
-        const char *e = getenv("MK_ILU_FUSE_ROWS");              // (read at every creation: tests switch it)
-        if (e && *e) F->fuse = atoi(e) > 0 ? atoi(e) : 0;
-    }
+    static_assert(mk_switch_table[MK_SW_ILU_FUSE_ROWS].dflt == MK_ILU_FUSE_DEFAULT, "one default");
+    F->fuse = (int)mk_switch_int<MK_SW_ILU_FUSE_ROWS>();     // (read at every creation: tests switch it)
     std::vector<int32_t> rows_f, off_f, rows_b, off_b;
     mk_ilu_levels(ip, ix, dg, true, rows_f, off_f);
     mk_ilu_levels(ip, ix, dg, false, rows_b, off_b);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mikrylov.h"
+#include "mk_switch.h"
 
 // --------------------------------------------------------------------------------------
 // geometry shared by every kernel

@@ -338,7 +338,7 @@ static inline int mk_launch_spmv(mk_solver *s, const double *x, const Epi &epi, 
     const MkPlan *plan = A->ex.pending ? mk_csr_plan(A) : nullptr;
     const bool march = plan && mk_fmt_march(plan->fmt);
     int za, zb;
-    const bool thin = MkSymMarch<Epi>::value && mk_pen_tail_gen();   // (mk_pen_split: only the first and the last plane wait)
+    const bool thin = MkSymMarch<Epi>::value;   // (mk_pen_split: only the first and the last plane wait)
     if (A->ex.pending && march && (!mk_march_kernel_for<Epi>(plan) || !mk_pen_split(plan, &za, &zb, thin))) {
         // a slab of too few planes to split -- or a loop without a kernel for this march format, whose product runs as the
         // CSR gather kernel over ALL rows (a plane range means nothing to it): the messages first, then one launch
