@@ -46,13 +46,8 @@ struct MkCsrView {
     int64_t ntl;
     int poff;
     int part;
-    // windowed tile format (mk_format.hip); fmt 0: none of this is read
-    int fmt;                 // 0 plain CSR (gathers), 1 windows + uint16 LDS slots, 2 windows + slots + value dictionary,
-                             // 3 plain CSR with the tile resident in LDS and the gathers ordered by column block,
-                             // 4 windows + dictionary + one pattern byte per row instead of a word per nonzero,
-                             // 5 windows + pattern byte per row + the raw values streamed in tile-sliced ELL order
-                             // 6 / 7 / 8 wide tiles (rows <= 32 entries, <= 32 chunks): slots + values streamed /
-                             // pattern byte + values streamed / pattern byte + dictionary
+    // windowed tile format (mk_format.hip); MK_ST_CSR: none of this is read
+    int fmt;                 // storage format (MkStorage, mk_variant.h)
     int wchunks;             // LDS chunks (128 doubles each) reserved for the x windows of a tile
     int ndict;
     const uint16_t *slots;   // per nonzero: position of its x entry in the tile's LDS window buffer
@@ -163,11 +158,8 @@ static inline int mk_tile_map(const mk_csr *A) {
     // runs into the fabric on re-fetched x windows: XCD-contiguous blocks within every step of the grid keep neighbouring
     // tiles' windows in one L2 (512^3: fabric reads 4.4 -> 3.6 GB, 838 -> 790 us)
     const MkPlan *P = mk_csr_plan(A);
-    return (P && P->fmt >= 4) ? 2 : 0;
+    return (P && (mk_fmt_pattern(P->fmt) || mk_fmt_march(P->fmt))) ? 2 : 0;
 }
-
-constexpr int MK_PROD_LD = MK_BLOCK + 1;             // (product staging buffer of the SpMV kernels, see below)
-constexpr int MK_PROD_LDS = 8 * MK_PROD_LD;          // doubles reserved for products (>= MK_SPMV_TILE of the gather path)
 
 int mk_host_product(const mk_csr *A, hipStream_t st);   // mk_core.hip: D2H, host callback, H2D of a matrix-free operator
 
@@ -184,7 +176,7 @@ static inline int mk_grid_spmv_for(const mk_csr *A) {
     if (mk_switch<MK_SW_GRID_SPMV>().set || A->host_fn) return g;
     const MkPlan *P = mk_csr_plan(A);
     int64_t cap = mk_cap_spmv();
-    if (P && P->cblocks.size() >= 2 && P->cblocks[0]->plan.fmt == 3 && A->ex.mode < 0) {   // column blocks as resident tiles
+    if (P && P->cblocks.size() >= 2 && P->cblocks[0]->plan.fmt == MK_ST_RESIDENT && A->ex.mode < 0) {   // column blocks as resident tiles
         int g3 = (int)(A->ntiles > MK_MAXP ? MK_MAXP : A->ntiles);
         if (g3 >= 8) g3 -= g3 % 8;
         return g3;
@@ -193,31 +185,17 @@ static inline int mk_grid_spmv_for(const mk_csr *A) {
         const int64_t items = (int64_t)(P->pen_per > 0 ? 8 * P->pen_per : P->pen_bpp) * P->pen_chunks;
         return (int)(items > MK_MAXP ? MK_MAXP : items);
     }
-    if (P && P->fmt == 3) {                                  // as many as fit at once with one tile in LDS each
+    if (P && P->fmt == MK_ST_RESIDENT) {                               // as many as fit at once with one tile in LDS each
         int g3 = (int)(A->ntiles > MK_MAXP ? MK_MAXP : A->ntiles);
         if (g3 >= 8) g3 -= g3 % 8;
         return g3;
     }
-    if (P && (P->fmt == 4 || P->fmt == 5)) {                 // up to 7 per CU, as many as LDS holds (8 per CU: 512^3 +3 %,
-                                                             // 2-D n = 1e6 -4 %, and MINRES' epilogue spills at 64 registers)
-        int64_t top = 128 * (int64_t)P->wchunks + 2;
-        if (P->covered != A->ntiles && top < MK_PROD_LDS) top = MK_PROD_LDS;
-        const int64_t lds = 8 * (top + MK_BLOCK) + (P->fmt == 4 ? 16 : 4) * (int64_t)(P->npat * P->pmax + 4) + 2560;   // + static arrays
-        int64_t per_cu = (160 * 1024) / lds;
-        per_cu = per_cu > 7 ? 7 : (per_cu < 1 ? 1 : per_cu);
-        cap = 256 * per_cu;
-    }
-    else if (P && P->fmt >= 6) {                             // wide tiles: 4 per CU (128 registers; fmt 8: 7), as many as LDS holds
-        int64_t top = 128 * (int64_t)P->wchunks + 2;
-        if (P->covered != A->ntiles && top < MK_PROD_LDS) top = MK_PROD_LDS;
-        const int64_t lds = 8 * (top + MK_BLOCK) + 4 * (int64_t)((P->fmt == 7 ? P->npat * P->pmax : 0) + 4) + 2560;   // + static arrays
-        int64_t per_cu = (160 * 1024) / lds;
-        const int64_t top_cu = (P->fmt == 8) ? 7 : 4;
-        per_cu = per_cu > top_cu ? top_cu : (per_cu < 1 ? 1 : per_cu);
-        cap = 256 * per_cu;
-    }
-    else if (P && P->fmt == 2) cap = mk_xcd_chunks(A) ? 1280 : 1024;
-    else if (P && P->fmt == 1) cap = 1024;
+    if (P && mk_fmt_pattern(P->fmt))                         // up to 7 per CU (wide tiles with streamed values: 4, 128 registers),
+                                                             // as many as LDS holds (8 per CU: 512^3 +3 %, 2-D n = 1e6 -4 %,
+                                                             // and MINRES' epilogue spills at 64 registers)
+        cap = 256 * mk_spmv_per_cu(P->fmt, P->wchunks, P->covered == A->ntiles, P->npat, P->pmax);
+    else if (P && P->fmt == MK_ST_DICT) cap = mk_xcd_chunks(A) ? 1280 : 1024;
+    else if (P && P->fmt == MK_ST_WIN) cap = 1024;
     else if (mk_xcd_chunks(A)) cap = 2 * cap > MK_MAXP ? MK_MAXP : 2 * cap;
     g = (int)(A->ntiles > cap ? cap : (A->ntiles < 1 ? 1 : A->ntiles));
     if (g >= 8) g -= g % 8;
@@ -261,7 +239,7 @@ static inline MkCsrView mk_view(const mk_csr *A) {
     v.poff = 0;
     v.part = 0;
     const MkPlan *P = mk_csr_plan(A);
-    v.fmt = P ? P->fmt : 0;
+    v.fmt = P ? P->fmt : MK_ST_CSR;
     if (mk_fmt_march(v.fmt)) {
         v.pid = P->d_pid;
         v.sval = P->d_sval;                                  // (format 10: seven value arrays, position major)
@@ -284,13 +262,13 @@ static inline MkCsrView mk_view(const mk_csr *A) {
         v.pen_nol = P->pen_nol;
         v.pen_xtop = A->x_len() - 1;
         v.pen_dump = P->pen_gen ? mk_pen_dump() : nullptr;
-    } else if (v.fmt == 3) {
+    } else if (v.fmt == MK_ST_RESIDENT) {
         v.rt_cap = P->rt_cap;
         v.rt_k = P->rt_k;
         v.rt_w = P->rt_w;
         v.rt_reg = P->rt_reg;
         v.carry = P->d_carry;
-    } else if (v.fmt) {
+    } else if (v.fmt != MK_ST_CSR) {
         v.wchunks = P->wchunks;
         v.ndict = P->ndict;
         v.slots = P->d_slots;
@@ -307,7 +285,7 @@ static inline MkCsrView mk_view(const mk_csr *A) {
         v.sdesc = P->d_sdesc;
         v.allwin = (P->covered == A->ntiles) ? 1 : 0;
         v.wper = P->wide ? 8 : 4;
-        v.wmode = v.fmt >= 6 ? v.fmt - 6 : 0;
+        v.wmode = mk_fmt_wide(v.fmt) ? v.fmt - MK_ST_WIDE_SLOT : 0;
         v.sslot = P->d_sslot;
         v.ptab = P->d_ptab;
         v.pinfo = P->d_pinfo;
@@ -667,23 +645,12 @@ __device__ __forceinline__ void mk_load_meta(const MkCsrView &A, int64_t p, int6
 #include "mk_spmv_fmtw.h"
 #include "mk_spmv_fmt9.h"
 
-constexpr int MK_FMT_WIDE = 7;                       // template values of the wide kernels (6 = format 5, non-temporal):
-constexpr int MK_FMT_WIDE_DICT = 8;                  // 7 streams values (fmt 6, 7), 8 takes them from the dictionary (fmt 8),
-constexpr int MK_FMT_WIDE_NT = 9;                    // 9 = 7 with non-temporal loads of the streams
-constexpr int MK_FMT_PAIR = 10;                      // format 3 with a second tile per workgroup in registers (rows <= 5 entries)
-constexpr int MK_FMT_PENCIL = 11;                    // format 9: z-marching bricks (mk_spmv_fmt9.h)
-constexpr int MK_FMT_PENCIL_STREAM = 12;             // format 10: the same march with streamed values (no dictionary)
-constexpr int MK_FMT_PENCIL_SYM = 13;                // format 11: ... of a symmetric matrix (diagonal and upper values only)
-constexpr int MK_FMT_PENCIL_G = 14;                  // formats 9 / 10 / 11 on a general geometry (mk_spmv_fmt9.h, GEN): 14 / 15 / 16
-constexpr int MK_FMT_PENCIL_STREAM_G = 15;
-constexpr int MK_FMT_PENCIL_SYM_G = 16;
-
 template <int FMT, bool PROG, class Epi, int NACC>
 __device__ __forceinline__ void mk_spmv_tiles(const MkCsrView &A, const double *__restrict__ x, Epi &epi,
                                               double *prod, double *xw, double (&acc)[NACC]) {
-    if constexpr (FMT == 0) mk_spmv_tiles_fmt0<PROG>(A, x, epi, prod, xw, acc);
-    else if constexpr (FMT == 1) mk_spmv_tiles_fmt1<PROG>(A, x, epi, prod, xw, acc);
-    else if constexpr (FMT == 3) mk_spmv_tiles_fmt3<PROG>(A, x, epi, prod, xw, acc);
+    if constexpr (FMT == MK_FMT_CSR) mk_spmv_tiles_fmt0<PROG>(A, x, epi, prod, xw, acc);
+    else if constexpr (FMT == MK_FMT_WIN) mk_spmv_tiles_fmt1<PROG>(A, x, epi, prod, xw, acc);
+    else if constexpr (FMT == MK_FMT_RESIDENT) mk_spmv_tiles_fmt3<PROG>(A, x, epi, prod, xw, acc);
     else if constexpr (FMT == MK_FMT_PAIR) mk_spmv_tiles_fmt3r<5, PROG>(A, x, epi, prod, xw, acc);
     else if constexpr (FMT == MK_FMT_PENCIL) mk_spmv_tiles_fmt9<PROG, false, false, false>(A, x, epi, xw, acc);
     else if constexpr (FMT == MK_FMT_PENCIL_STREAM) mk_spmv_tiles_fmt9<PROG, true, false, false>(A, x, epi, xw, acc);
@@ -693,7 +660,7 @@ __device__ __forceinline__ void mk_spmv_tiles(const MkCsrView &A, const double *
     else if constexpr (FMT == MK_FMT_PENCIL_SYM_G) mk_spmv_tiles_fmt9<PROG, true, true, true>(A, x, epi, xw, acc);
     else if constexpr (FMT == MK_FMT_WIDE || FMT == MK_FMT_WIDE_DICT || FMT == MK_FMT_WIDE_NT)
         mk_spmv_tiles_wide<FMT == MK_FMT_WIDE_DICT, FMT == MK_FMT_WIDE_NT, PROG>(A, x, epi, prod, xw, acc);
-    else if constexpr (FMT >= 5) mk_spmv_tiles_fmt5<PROG, FMT == 6>(A, x, epi, prod, xw, acc);
+    else if constexpr (FMT == MK_FMT_PAT_STREAM || FMT == MK_FMT_PAT_STREAM_NT) mk_spmv_tiles_fmt5<PROG, FMT == MK_FMT_PAT_STREAM_NT>(A, x, epi, prod, xw, acc);
     else mk_spmv_tiles_fmt24<FMT, PROG>(A, x, epi, prod, xw, acc);
 }
 
@@ -705,13 +672,14 @@ struct MkNoGate {
 };
 
 template <class Epi, class Gate, bool PROG, int FMT>
-__global__ __launch_bounds__(MK_BLOCK, (FMT == 0 || FMT == 3 || FMT == 10) ? 8 : ((FMT >= 11 && FMT <= 16) ? MK_PEN_OCC : ((FMT == 7 || FMT == 9) ? 4 : (FMT >= 4 ? 7 : 4)))) void mk_spmv_kernel(MkCsrView A, const double *__restrict__ x, Epi epi,
+__global__ __launch_bounds__(MK_BLOCK, mk_variant_table[FMT].min_blocks) void mk_spmv_kernel(MkCsrView A, const double *__restrict__ x, Epi epi,
                                                            Gate gate, MkHalt halt, double *__restrict__ partials) {
-    // fmt 0 / 1: products [MK_PROD_LDS doubles], then the windows.  fmt 2 has no product staging: its windows and
-    // packed words share the space the gather path of uncovered tiles uses for products (never live together)
+    constexpr MkVariantRow V = mk_variant_table[FMT];
+    // products [MK_PROD_LDS doubles], then the windows -- or (V.xw_alias) no product staging: the windows share the space
+    // the gather path of uncovered tiles uses for products (never live together)
     extern __shared__ __attribute__((aligned(16))) double mk_smem[];
     double *prod = mk_smem;
-    double *xw = (FMT == 2 || (FMT >= 4 && FMT != 10)) ? mk_smem : mk_smem + MK_PROD_LDS;
+    double *xw = V.xw_alias ? mk_smem : mk_smem + MK_PROD_LDS;
     __shared__ double s4[4];
     const bool halted = halt.in();
     const bool lead = (blockIdx.x == 0 && threadIdx.x == 0);
@@ -722,7 +690,7 @@ __global__ __launch_bounds__(MK_BLOCK, (FMT == 0 || FMT == 3 || FMT == 10) ? 8 :
     bool stop = false;
     const bool go = gate.open(s4, lead && A.part != 2, &stop);     // part 2 repeats the decision, not the writes
     if (lead) halt.out(stop);
-    if constexpr (FMT == 0 && !PROG) {
+    if constexpr (FMT == MK_FMT_CSR && !PROG) {
         if (lead && A.cb_mode == 1) *A.cb_go = go ? 1 : 0;          // (zeroed by the host before the launch)
     }
     if (!go) return;
@@ -730,13 +698,13 @@ __global__ __launch_bounds__(MK_BLOCK, (FMT == 0 || FMT == 3 || FMT == 10) ? 8 :
     double acc[Epi::NACC > 0 ? Epi::NACC : 1];
 #pragma unroll
     for (int d = 0; d < (Epi::NACC > 0 ? Epi::NACC : 1); ++d) acc[d] = 0.0;
-    if constexpr (FMT == 10 && Epi::NACC > 0) {
+    if constexpr (V.carry && Epi::NACC > 0) {
         if (A.carry_in) {                                           // a later step of a product split into launches
 #pragma unroll
             for (int d = 0; d < Epi::NACC; ++d) acc[d] = A.carry[((size_t)d * gridDim.x + blockIdx.x) * MK_BLOCK + threadIdx.x];
         }
     }
-    if constexpr (FMT == 0 && !PROG) {
+    if constexpr (FMT == MK_FMT_CSR && !PROG) {
         if (A.cb_mode == 1) {                                       // matrix-free operator: the callback's input
             for (int64_t j = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; j < A.xlen; j += (int64_t)gridDim.x * MK_BLOCK)
                 A.vin[j] = epi.xin(x[j]);
@@ -756,7 +724,7 @@ __global__ __launch_bounds__(MK_BLOCK, (FMT == 0 || FMT == 3 || FMT == 10) ? 8 :
     } else {
         mk_spmv_tiles<FMT, PROG>(A, x, epi, prod, xw, acc);
     }
-    if constexpr (FMT == 10) {
+    if constexpr (V.carry) {
         if (A.carry_out) {                                          // not the last step: the accumulators travel on
             if constexpr (Epi::NACC > 0) {
 #pragma unroll
@@ -773,121 +741,64 @@ __global__ __launch_bounds__(MK_BLOCK, (FMT == 0 || FMT == 3 || FMT == 10) ? 8 :
     if (A.part != 1) halt.template clear_tail<Epi::NACC, Epi::SLOT0>(partials, A.poff + (int)gridDim.x);
 }
 
+template <int K>
+using MkK = std::integral_constant<int, K>;
+
 // does this loop's epilogue have a kernel for the plan's march format?  (No: mk_spmv_launch_fmt runs the CSR gather kernel
 // on the matrix's arrays instead -- over all rows, so a caller must not cut such a product into plane ranges.)
 template <class Epi>
 static inline bool mk_march_kernel_for(const MkPlan *P) {
-    if (!P || !mk_fmt_march(P->fmt) || MkNoMarch<Epi>::value) return false;
-    return MkSymMarch<Epi>::value || (P->fmt != 11 && P->pen_gen != 2);
+    return P && mk_variant_march(mk_spmv_variant(P->fmt, 0, 0, false, P->pen_gen, MkNoMarch<Epi>::value, MkSymMarch<Epi>::value,
+                                                 MkMarchOnly<Epi>::value));
 }
 
-// Launch the instantiation that matches the operator: plain matrices never pay for the row program, matrices
+// Launch the instantiation that matches the operator (mk_variant.h): plain matrices never pay for the row program, matrices
 // without windowed tiles never pay for the window code.
 template <class Epi, class Gate, bool PROG>
 static inline void mk_spmv_launch_fmt(const MkCsrView &v, int grid, hipStream_t st, const double *x, const Epi &epi,
                                       const Gate &gate, MkHalt halt, double *partials) {
-    size_t lds = sizeof(double) * (size_t)(MK_PROD_LDS + (v.fmt == 1 ? 128 * v.wchunks + 2 : 0));
-    if (v.fmt == 2) {                                        // windows + packed words, or the gather path's products
-        const size_t w = sizeof(double) * (size_t)(128 * v.wchunks + 2) + sizeof(uint32_t) * (MK_SPMV_TILE + 16);
-        lds = w > lds ? w : lds;
-    }
-    if constexpr (MkMarchOnly<Epi>::value) {
-        static_assert(MkSymMarch<Epi>::value && !MkNoMarch<Epi>::value && !PROG, "a march-only epilogue has all six march kernels and no row program");
-        if (!mk_fmt_march(v.fmt)) {
-            const int rc = mk_fail(MK_ERR_STATE, "a march-only product kernel was launched on storage format %d", v.fmt);
-            if (mk_ctx().pending_rc == MK_OK) mk_ctx().pending_rc = rc;
-            return;
-        }
-    } else if (mk_fmt_march(v.fmt) && (MkNoMarch<Epi>::value || ((v.fmt == 11 || v.pen_gen == 2) && !MkSymMarch<Epi>::value))) {
-        MkCsrView w = v;                                     // (see MkNoMarch: a format forced by hand on a loop that has no such kernel)
-        w.fmt = 0;
-        hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, 0>), dim3(grid), dim3(MK_BLOCK), lds, st, w, x, epi, gate, halt, partials);
+    constexpr bool NM = MkNoMarch<Epi>::value, SM = MkSymMarch<Epi>::value, MO = MkMarchOnly<Epi>::value;
+    static_assert(!MO || (SM && !NM && !PROG), "a march-only epilogue has all six march kernels and no row program");
+    const int k = mk_spmv_variant(v.fmt, v.nt, v.rt_reg, v.tiles != nullptr, v.pen_gen, NM, SM, MO);
+    if (k == MK_FMT_NONE) {
+        const int rc = mk_fail(MK_ERR_STATE, "a march-only product kernel was launched on storage format %d", v.fmt);
+        if (mk_ctx().pending_rc == MK_OK) mk_ctx().pending_rc = rc;
         return;
     }
-    if (mk_fmt_march(v.fmt)) {
-        if constexpr (MkSymMarch<Epi>::value) {              // general geometry / masked leftover round (mk_spmv_fmt9.h, GEN)
-            if (v.pen_gen) {
-                if (v.fmt == 9) {
-                    lds = sizeof(double) * (size_t)MK_PEN_LDS + 64 * (size_t)v.npat;
-                    hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, MK_FMT_PENCIL_G>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi,
-                                       gate, halt, partials);
-                } else if (v.fmt == 10) {
-                    lds = sizeof(double) * (size_t)MK_PEN_LDS;
-                    hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, MK_FMT_PENCIL_STREAM_G>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x,
-                                       epi, gate, halt, partials);
-                } else {
-                    lds = sizeof(double) * (size_t)MK_PEN_LDS_SYM;
-                    hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, MK_FMT_PENCIL_SYM_G>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x,
-                                       epi, gate, halt, partials);
-                }
-                return;
-            }
-        }
-        if constexpr (!MkNoMarch<Epi>::value) {
-            if (v.fmt == 9) {                                // two plane images of the brick + the dump row
-                lds = sizeof(double) * (size_t)MK_PEN_LDS + 64 * (size_t)v.npat;
-                hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, MK_FMT_PENCIL>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi,
-                                   gate, halt, partials);
-            } else if (v.fmt == 10) {                        // ... the same without a pattern table
-                lds = sizeof(double) * (size_t)MK_PEN_LDS;
-                hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, MK_FMT_PENCIL_STREAM>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x,
-                                   epi, gate, halt, partials);
-            } else if constexpr (MkSymMarch<Epi>::value) {   // ... of a symmetric matrix: + the image of the plane's values
-                lds = sizeof(double) * (size_t)MK_PEN_LDS_SYM;
-                hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, MK_FMT_PENCIL_SYM>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x,
-                                   epi, gate, halt, partials);
-            }
-        }
+    const size_t lds = mk_spmv_lds_bytes(k, v.fmt, v.wchunks, v.allwin, v.npat, v.pmax, v.rt_cap);
+    using Kernel = void (*)(MkCsrView, const double *, Epi, Gate, MkHalt, double *);
+    auto instance = [](auto K) -> Kernel {                   // (null: variant K is not compiled for this epilogue and never chosen for it)
+        if constexpr (mk_variant_compiled(decltype(K)::value, NM, SM, MO, PROG)) return mk_spmv_kernel<Epi, Gate, PROG, decltype(K)::value>;
+        else return nullptr;
+    };
+    Kernel kernel = nullptr;
+    switch (k) {
+    case MK_FMT_CSR: kernel = instance(MkK<MK_FMT_CSR>{}); break;
+    case MK_FMT_WIN: kernel = instance(MkK<MK_FMT_WIN>{}); break;
+    case MK_FMT_DICT: kernel = instance(MkK<MK_FMT_DICT>{}); break;
+    case MK_FMT_RESIDENT: kernel = instance(MkK<MK_FMT_RESIDENT>{}); break;
+    case MK_FMT_PAT: kernel = instance(MkK<MK_FMT_PAT>{}); break;
+    case MK_FMT_PAT_STREAM: kernel = instance(MkK<MK_FMT_PAT_STREAM>{}); break;
+    case MK_FMT_PAT_STREAM_NT: kernel = instance(MkK<MK_FMT_PAT_STREAM_NT>{}); break;
+    case MK_FMT_WIDE: kernel = instance(MkK<MK_FMT_WIDE>{}); break;
+    case MK_FMT_WIDE_DICT: kernel = instance(MkK<MK_FMT_WIDE_DICT>{}); break;
+    case MK_FMT_WIDE_NT: kernel = instance(MkK<MK_FMT_WIDE_NT>{}); break;
+    case MK_FMT_PAIR: kernel = instance(MkK<MK_FMT_PAIR>{}); break;
+    case MK_FMT_PENCIL: kernel = instance(MkK<MK_FMT_PENCIL>{}); break;
+    case MK_FMT_PENCIL_STREAM: kernel = instance(MkK<MK_FMT_PENCIL_STREAM>{}); break;
+    case MK_FMT_PENCIL_SYM: kernel = instance(MkK<MK_FMT_PENCIL_SYM>{}); break;
+    case MK_FMT_PENCIL_G: kernel = instance(MkK<MK_FMT_PENCIL_G>{}); break;
+    case MK_FMT_PENCIL_STREAM_G: kernel = instance(MkK<MK_FMT_PENCIL_STREAM_G>{}); break;
+    case MK_FMT_PENCIL_SYM_G: kernel = instance(MkK<MK_FMT_PENCIL_SYM_G>{}); break;
+    }
+    if (!kernel) return;
+    if (k == MK_FMT_CSR && v.fmt != MK_ST_CSR) {             // (the fallback of mk_spmv_variant: the gather kernel on the same arrays)
+        MkCsrView w = v;
+        w.fmt = MK_ST_CSR;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(MK_BLOCK), lds, st, w, x, epi, gate, halt, partials);
         return;
     }
-    if constexpr (!MkMarchOnly<Epi>::value) {
-    if (v.fmt == 4) {                                        // windows + pattern table, or the gather path's products
-        size_t wtop = (size_t)(128 * v.wchunks + 2);
-        if (!v.allwin && wtop < (size_t)MK_PROD_LDS) wtop = (size_t)MK_PROD_LDS;
-        lds = sizeof(double) * (wtop + MK_BLOCK) + 16 * (size_t)(v.npat * v.pmax + 1);   // windows, zeros, table
-        hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, 4>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi, gate,
-                           halt, partials);
-    } else if (v.fmt == 5) {                                 // windows + zeros + offset table, or the gather path's products
-        size_t wtop = (size_t)(128 * v.wchunks + 2);
-        if (!v.allwin && wtop < (size_t)MK_PROD_LDS) wtop = (size_t)MK_PROD_LDS;
-        lds = sizeof(double) * (wtop + MK_BLOCK) + 4 * (size_t)(v.npat * v.pmax + 4);
-        if (v.nt)                                       // (template value 6 = format 5 with non-temporal value loads)
-            hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, 6>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi, gate,
-                               halt, partials);
-        else
-            hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, 5>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi, gate,
-                               halt, partials);
-    } else if (v.fmt >= 6) {                                 // wide tiles: zeros + windows (or the gather path's products) + pattern words
-        size_t wtop = (size_t)(128 * v.wchunks + 2);
-        if (!v.allwin && wtop < (size_t)MK_PROD_LDS) wtop = (size_t)MK_PROD_LDS;
-        lds = sizeof(double) * (wtop + MK_BLOCK) + 4 * (size_t)((v.fmt == 7 ? v.npat * v.pmax : 0) + 4);
-        if (v.fmt == 8)
-            hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, MK_FMT_WIDE_DICT>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x,
-                               epi, gate, halt, partials);
-        else if (v.nt)
-            hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, MK_FMT_WIDE_NT>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x,
-                               epi, gate, halt, partials);
-        else
-            hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, MK_FMT_WIDE>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi,
-                               gate, halt, partials);
-    } else if (v.fmt == 3) {                                 // the tile's values and columns
-        lds = (size_t)v.rt_cap * 12;
-        if (v.rt_reg && !v.tiles)
-            hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, MK_FMT_PAIR>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi,
-                               gate, halt, partials);
-        else
-            hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, 3>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi, gate,
-                               halt, partials);
-    } else if (v.fmt == 2)
-        hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, 2>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi, gate,
-                           halt, partials);
-    else if (v.fmt == 1)
-        hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, 1>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi, gate,
-                           halt, partials);
-    else
-        hipLaunchKernelGGL((mk_spmv_kernel<Epi, Gate, PROG, 0>), dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi, gate,
-                           halt, partials);
-    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(MK_BLOCK), lds, st, v, x, epi, gate, halt, partials);
 }
 
 template <class Epi, class Gate>
@@ -1093,7 +1004,7 @@ static inline void mk_spmv_launch_blocks(const mk_csr *A, int grid, hipStream_t 
         // fused dots travel through a carry buffer (same additions in the same order: same bits), the last launch reduces.
         const int64_t per = 2 * (int64_t)grid;
         const int64_t steps = (v.ntl + per - 1) / per;
-        if (v.fmt == 3 && v.rt_reg && !v.tiles && v.carry && v.map == 0 && steps >= 2 && steps <= 64 && Epi::NACC <= MK_CARRY_SLOTS) {
+        if (v.fmt == MK_ST_RESIDENT && v.rt_reg && !v.tiles && v.carry && v.map == 0 && steps >= 2 && steps <= 64 && Epi::NACC <= MK_CARRY_SLOTS) {
             for (int64_t k = 0; k < steps; ++k) {
                 MkCsrView w = v;
                 w.step0 = (int)k;
@@ -1114,8 +1025,8 @@ static inline void mk_spmv_launch_blocks(const mk_csr *A, int grid, hipStream_t 
         v.indptr = B->d_indptr;
         v.indices = B->d_indices;
         v.data = B->d_data;
-        if (B->plan.fmt == 3) {                              // (resident tiles, one phase: mk_format.hip cblocks_build)
-            v.fmt = 3;
+        if (B->plan.fmt == MK_ST_RESIDENT) {                             // (resident tiles, one phase: mk_format.hip cblocks_build)
+            v.fmt = MK_ST_RESIDENT;
             v.rt_cap = B->plan.rt_cap;
             v.rt_k = B->plan.rt_k;
             v.rt_w = B->plan.rt_w;

@@ -616,7 +616,7 @@ int cblocks_build(const mk_csr *A, int64_t blk_override = 0) {
         mk_csr *B = P.cblocks[bi];
         plan_free(B->plan);
         B->plan.built = true;
-        if (resident_plan(B, B->plan, true) != MK_OK || B->plan.fmt != 3) all = false;
+        if (resident_plan(B, B->plan, true) != MK_OK || B->plan.fmt != MK_ST_RESIDENT) all = false;
         hipFree(B->plan.d_carry);                            // (a block never runs as a stepped pair product)
         B->plan.d_carry = nullptr;
         // phases over the block's OWN slice of x (bw columns from b * bw), 1.5 MiB each: a slice larger than an L2's share
@@ -699,7 +699,7 @@ int resident_plan(const mk_csr *A, MkPlan &P, bool forced) {
     int64_t k = (xbytes + slice - 1) / slice;
     if (mk_switch_int<MK_SW_RT_PHASES>() > 0) k = mk_switch_int<MK_SW_RT_PHASES>();
     k = k < 1 ? 1 : (k > 64 ? 64 : k);
-    P.fmt = 3;
+    P.fmt = MK_ST_RESIDENT;
     P.rt_cap = cap;
     P.rt_k = (int)k;
     P.rt_w = (int)((A->x_len() + k - 1) / k);
@@ -884,7 +884,7 @@ bool pattern_plan(const mk_csr *A, MkPlan &P, bool raw) {
     d_plen = nullptr;
     P.npat = count;
     P.pmax = pmax;
-    P.fmt = P.wide ? (raw ? 7 : 8) : (raw ? 5 : 4);
+    P.fmt = P.wide ? (raw ? MK_ST_WIDE_PAT : MK_ST_WIDE_DICT) : (raw ? MK_ST_PAT_STREAM : MK_ST_PAT);
     if (mk_switch_flag<MK_SW_DEBUG_PLAN>()) fprintf(stderr, "mikrylov: %lld rows, %d row patterns of <= %d entries (fmt %d)\n", (long long)A->nrows, count, pmax, P.fmt);
     // the per-nonzero streams are not read any more (tiles without windows gather from the CSR arrays)
     hipFree(P.d_pk);
@@ -1288,7 +1288,7 @@ bool pencil_plan(const mk_csr *A, MkPlan &P, bool forced, int want) {
     int gnz = (int)((A->nnz + MK_BLOCK - 1) / MK_BLOCK);
     hipLaunchKernelGGL(dict_collect, dim3(gnz > 512 ? 512 : gnz), dim3(MK_BLOCK), 0, st, A->nnz, A->d_data, d_table, d_state);
     auto stream_twin = [&]() -> bool {                      // format 10: mask byte + seven value arrays
-        if (want < 10) return drop();
+        if (want < MK_ST_MARCH_STREAM) return drop();
         double *d_sval = nullptr;
         if (hipMalloc((void **)&d_pid, (size_t)A->nrows + 64 + slack) != hipSuccess ||
             hipMalloc((void **)&d_sval, sizeof(double) * (7 * (size_t)A->nrows + slack) + 64) != hipSuccess) {
@@ -1304,9 +1304,9 @@ bool pencil_plan(const mk_csr *A, MkPlan &P, bool forced, int want) {
             hipFree(d_sval);
             return drop();
         }
-        P.fmt = 10;
+        P.fmt = MK_ST_MARCH_STREAM;
         P.sell_entries = 7 * A->nrows;
-        if (want >= 11) {                                    // format 11: symmetric bit for bit? then 4 of the 7 arrays do
+        if (want >= MK_ST_MARCH_SYM) {                                 // format 11: symmetric bit for bit? then 4 of the 7 arrays do
             double *d_sym = nullptr;
             hipMemsetAsync(d_state, 0, 2 * sizeof(int), st);
             hipLaunchKernelGGL(pen_sym_check, dim3(grid), dim3(MK_BLOCK), 0, st, A->nrows, L, PP, A->loc_lo ? PP : (int64_t)0,
@@ -1318,7 +1318,7 @@ bool pencil_plan(const mk_csr *A, MkPlan &P, bool forced, int want) {
                 if (hipStreamSynchronize(st) == hipSuccess && hipGetLastError() == hipSuccess) {
                     hipFree(d_sval);
                     d_sval = d_sym;
-                    P.fmt = 11;
+                    P.fmt = MK_ST_MARCH_SYM;
                     P.sell_entries = 4 * A->nrows + PP;
                 } else {
                     hipFree(d_sym);
@@ -1360,7 +1360,7 @@ bool pencil_plan(const mk_csr *A, MkPlan &P, bool forced, int want) {
     hipFree(d_stats);
     hipFree(d_table);
     hipFree(d_keys);
-    P.fmt = 9;
+    P.fmt = MK_ST_MARCH;
     P.d_pid = d_pid;
     P.d_ptab = d_tab;
     P.d_dict = d_dict;
@@ -1382,9 +1382,9 @@ bool pencil_plan(const mk_csr *A, MkPlan &P, bool forced, int want) {
 int plan_build(const mk_csr *A) {
     MkPlan &P = A->plan;
     P.built = true;
-    P.fmt = 0;
-    int want = A->want_fmt >= 0 ? A->want_fmt : default_format();
-    if (want == 11 && A->no_sym) want = 10;                  // (format 11 has kernels for plain products and CG only)
+    P.fmt = MK_ST_CSR;
+    int want = A->want_fmt >= MK_ST_CSR ? A->want_fmt : default_format();   // (-1: the library default)
+    if (want == MK_ST_MARCH_SYM && A->no_sym) want = MK_ST_MARCH_STREAM;                 // (format 11 has kernels for plain products and CG only)
     if (A->nnz == 0 || A->ntiles == 0 || !mk_ctx().ready || A->host_fn || A->comp_kind) return MK_OK;
     auto plain = [&]() -> int {                              // plain CSR: x too long for an L2?
         if (cblocks_build(A) != MK_OK) {                     // (separate launches per column block: off by default)
@@ -1393,34 +1393,34 @@ int plan_build(const mk_csr *A) {
             hipFree(P.d_cbsum);
             P.d_cbsum = nullptr;
         }
-        if (P.cblocks.empty() && want != 0) return resident_plan(A, P, want == 3);
+        if (P.cblocks.empty() && want != MK_ST_CSR) return resident_plan(A, P, want == MK_ST_RESIDENT);
         return MK_OK;
     };
-    if (want == 0 || want == 3) return plain();
-    if (want >= 9 && (A->march_pref != 0 || A->want_fmt >= 9) && pencil_plan(A, P, A->want_fmt >= 9, want))
+    if (mk_fmt_plain(want)) return plain();
+    if (want >= MK_ST_MARCH && (A->march_pref != 0 || mk_fmt_march(A->want_fmt)) && pencil_plan(A, P, mk_fmt_march(A->want_fmt), want))
         return MK_OK;                                        // fmt 9 / 10: 7-point-class matrices (mk_csr_march_pref)
     auto fail = [&](const char *what) {
         plan_free(P);
         P.built = true;
         return mk_fail(MK_ERR_HIP, "windowed format: %s failed (the matrix stays on the CSR path)", what);
     };
-    const bool force_wide = (A->want_fmt == 6 || A->want_fmt == 7);
+    const bool force_wide = (A->want_fmt == MK_ST_WIDE_SLOT || A->want_fmt == MK_ST_WIDE_PAT);
     if (!cover_build(A, P, false)) return fail("cover kernel");
     const bool narrow_ok = 2 * P.covered >= A->ntiles;
     if (narrow_ok && !force_wide) {
-        P.fmt = 1;
-        if (want < 2) return MK_OK;
+        P.fmt = MK_ST_WIN;
+        if (want < MK_ST_DICT) return MK_OK;
         const int rc = dictionary_build(A, P);
         if (rc < 0) return fail("value dictionary");
         if (rc == 0) {                                       // too many distinct values: windows with raw values
-            if (want >= 5) pattern_plan(A, P, true);         // ... in pattern order when the rows follow patterns (fmt 5)
+            if (want >= MK_ST_PAT_STREAM) pattern_plan(A, P, true);       // ... in pattern order when the rows follow patterns (fmt 5)
             return MK_OK;
         }
-        P.fmt = 2;
-        if (want >= 4) pattern_plan(A, P, false);
+        P.fmt = MK_ST_DICT;
+        if (want >= MK_ST_PAT) pattern_plan(A, P, false);
         return MK_OK;
     }
-    if (want < 6) {                                          // mostly scattered columns or long rows: the CSR path
+    if (want < MK_ST_WIDE_SLOT) {                                       // mostly scattered columns or long rows: the CSR path
         plan_free(P);
         P.built = true;
         return plain();
@@ -1434,7 +1434,7 @@ int plan_build(const mk_csr *A) {
         P.built = true;
         return plain();
     }
-    if (want >= 8) {
+    if (want >= MK_ST_WIDE_DICT) {
         const int rc = dictionary_build(A, P);
         if (rc < 0) return fail("value dictionary");
         if (rc > 0) {
@@ -1446,9 +1446,9 @@ int plan_build(const mk_csr *A) {
             P.ndict = 0;
         }
     }
-    if (want >= 7 && pattern_plan(A, P, true)) return MK_OK; // fmt 7
+    if (want >= MK_ST_WIDE_PAT && pattern_plan(A, P, true)) return MK_OK; // fmt 7
     if (sell_build(A, P, 4, true)) {                         // fmt 6
-        P.fmt = 6;
+        P.fmt = MK_ST_WIDE_SLOT;
         hipFree(P.d_slots);                                  // (the kernel reads the slots from their ELL copy)
         P.d_slots = nullptr;
         return MK_OK;
@@ -1499,13 +1499,13 @@ void mk_csr_march_pref(const mk_csr *A, int pref) {
         const bool no_sym = (pref == 0);
         if (no_sym != o->no_sym) {
             o->no_sym = no_sym;
-            if (o->plan.built && ((no_sym && o->plan.fmt == 11) || (!no_sym && o->plan.fmt == 10 && o->want_fmt == 11))) {
+            if (o->plan.built && ((no_sym && o->plan.fmt == MK_ST_MARCH_SYM) || (!no_sym && o->plan.fmt == MK_ST_MARCH_STREAM && o->want_fmt == MK_ST_MARCH_SYM))) {
                 hipStreamSynchronize(mk_ctx().stream);
                 plan_free(o->plan);
             }
         }
     }
-    if (o->want_fmt >= 9 || o->comp_kind || o->host_fn) return;
+    if (mk_fmt_march(o->want_fmt) || o->comp_kind || o->host_fn) return;
     if (pinned) return;
     o->march_pref = pref;
     if (!o->plan.built) return;
@@ -1518,7 +1518,7 @@ void mk_csr_march_pref(const mk_csr *A, int pref) {
 
 extern "C" int mk_csr_set_format(mk_csr *A, int fmt) {
     MK_REQUIRE_INIT();
-    MK_ARG(A != nullptr && fmt >= -1 && fmt <= 11);
+    MK_ARG(A != nullptr && fmt >= -1 && fmt < MK_ST_COUNT);
     if (A->base) return mk_fail(MK_ERR_ARG, "mk_csr_set_format: set the format on the matrix a composed operator was built from");
     MK_HIP(hipStreamSynchronize(mk_ctx().stream));
     plan_free(A->plan);
@@ -1537,30 +1537,30 @@ extern "C" int mk_csr_format_info(const mk_csr *A, int32_t *fmt, int64_t *tiles_
         if (lds_chunks) *lds_chunks = 0;
         if (dict_size) *dict_size = P->ndict;
         if (matrix_bytes_per_product)
-            *matrix_bytes_per_product = A->nrows + (P->fmt == 9 ? 64 * (int64_t)P->npat : (P->fmt == 10 ? 56 : 32) * A->nrows);
+            *matrix_bytes_per_product = A->nrows + (P->fmt == MK_ST_MARCH ? 64 * (int64_t)P->npat : (P->fmt == MK_ST_MARCH_STREAM ? 56 : 32) * A->nrows);
         return MK_OK;
     }
-    const bool windowed = (P->fmt == 1 || P->fmt == 2 || P->fmt >= 4);
+    const bool windowed = mk_fmt_windowed(P->fmt);
     if (tiles_windowed) *tiles_windowed = windowed ? P->covered : 0;
-    if (lds_chunks) *lds_chunks = windowed ? P->wchunks : (P->fmt == 3 ? P->rt_k : 0);
+    if (lds_chunks) *lds_chunks = windowed ? P->wchunks : (P->fmt == MK_ST_RESIDENT ? P->rt_k : 0);
     if (dict_size) *dict_size = P->ndict;
     if (matrix_bytes_per_product) {
         // bytes of matrix data one product streams from HBM (x and y not included): per nonzero 4 + 8 (CSR),
         // 2 + 8 (windows) or 4 (windows + dictionary: one packed word), plus row pointers and the window descriptors
         int64_t b = 4 * (A->nrows + 1);
-        if (P->fmt == 0 || P->fmt == 3) b += 12 * A->nnz + (P->fmt == 3 ? 4 * A->nrows : 0);   // (fmt 3 reads every row pointer twice)
+        if (mk_fmt_plain(P->fmt)) b += 12 * A->nnz + (P->fmt == MK_ST_RESIDENT ? 4 * A->nrows : 0);   // (fmt 3 reads every row pointer twice)
         else {
             // nonzeros of windowed tiles are not kept; the mixed case is bounded by the covered share
             const double share = A->ntiles ? (double)P->covered / (double)A->ntiles : 0.0;
             // (fmt 4: one byte per ROW and no row pointers for the windowed tiles)
             // (fmt 5: the same byte per row, the padded values of the windowed tiles and 8 bytes per tile for their blocks)
             // (fmt 6, 7, 8: the wide twins -- fmt 6 streams padded values and padded uint16 slots and reads no pattern byte)
-            const double per = (P->fmt >= 4) ? 0.0 : ((P->fmt == 2) ? 4.0 : 10.0);
+            const double per = mk_fmt_pattern(P->fmt) ? 0.0 : ((P->fmt == MK_ST_DICT) ? 4.0 : 10.0);
             b += (int64_t)(A->nnz * (share * per + (1.0 - share) * 12.0)) + (P->wide ? 160 : 80) * A->ntiles;
-            if (P->fmt >= 4)
-                b += (int64_t)(P->fmt == 6 ? 0.0 : share * (double)A->nrows) - (int64_t)(share * 4.0 * (double)(A->nrows + 1));
-            if (P->fmt == 5) b += 8 * P->sell_entries + 8 * A->ntiles;
-            if (P->fmt == 6 || P->fmt == 7) b += 8 * P->sell_entries + 2 * P->slot_entries + 16 * A->ntiles;
+            if (mk_fmt_pattern(P->fmt))
+                b += (int64_t)(P->fmt == MK_ST_WIDE_SLOT ? 0.0 : share * (double)A->nrows) - (int64_t)(share * 4.0 * (double)(A->nrows + 1));
+            if (P->fmt == MK_ST_PAT_STREAM) b += 8 * P->sell_entries + 8 * A->ntiles;
+            if (P->fmt == MK_ST_WIDE_SLOT || P->fmt == MK_ST_WIDE_PAT) b += 8 * P->sell_entries + 2 * P->slot_entries + 16 * A->ntiles;
         }
         *matrix_bytes_per_product = b;
     }

@@ -11,15 +11,14 @@
 
 #include "../../include/mikrylov.h"
 #include "mk_switch.h"
+#include "mk_variant.h"
 
 // --------------------------------------------------------------------------------------
-// geometry shared by every kernel
+// geometry shared by every kernel (MK_BLOCK = 256 threads and MK_SPMV_TILE: mk_variant.h, with the LDS sizes they enter)
 // --------------------------------------------------------------------------------------
-constexpr int MK_BLOCK = 256;         // 4 wave64 per workgroup
 constexpr int MK_WAVE = 64;
 constexpr int MK_MAXP = 2048;         // partial-sum slots per reduction (= max grid of a producer)
 constexpr int MK_ROWS_PER_TILE = 256; // SpMV: one row per thread in the row-sum phase
-constexpr int MK_SPMV_TILE = 2048;    // SpMV: products staged in LDS per pass (16 KiB)
 constexpr int MK_NSCAL = 160;         // device scalar file per solver
 constexpr int MK_NDOT = 6;           // reduction slots per solver (MK_MAXP doubles each)
 constexpr int MK_CARRY_SLOTS = 4;     // fused dots whose per-lane accumulators a stepped product carries between its launches
@@ -101,16 +100,9 @@ constexpr int MK_WCHUNK = 128;     // doubles per window chunk (one wave-level 1
 constexpr int MK_WCHUNKS_MAX = 16; // chunks per tile (4 per wave): 16 KiB of LDS windows at most
 constexpr int MK_WCHUNKS_WIDE = 32; // ... of the wide cover (8 per wave, 32 KiB), tiles of up to MK_WIDE_TILE nonzeros
 constexpr int MK_WIDE_TILE = 8192;
-static inline bool mk_fmt_march(int fmt) { return fmt >= 9 && fmt <= 11; }   // the brick-march formats (mk_spmv_fmt9.h)
 struct MkPlan {
     bool built = false;
-    int fmt = 0;                   // 9 z-marching bricks: pattern byte per row + dictionary, 7-point-class matrices (below);
-                                   // 0 plain CSR, 1 windows + uint16 slots, 2 windows + slots + value dictionary,
-                                   // 3 plain CSR, tile resident in LDS, gathers ordered by column block,
-                                   // 4 windows + dictionary + row patterns (one byte per row)
-                                   // 5 windows + row patterns + raw values in tile-sliced ELL order
-                                   // 6 wide tiles: slots + values in tile-sliced ELL order; 7 wide: row patterns +
-                                   // values; 8 wide: row patterns + dictionary
+    int fmt = MK_ST_CSR;           // storage format (MkStorage, mk_variant.h)
     int wchunks = 0;               // max chunks of a tile
     int ndict = 0;
     int64_t covered = 0;           // tiles on the windowed path

@@ -11,7 +11,7 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt24(const MkCsrView &A, const do
     const int64_t stride = trange.stride, end = trange.end;
     __shared__ int sptr[MK_BLOCK + 1];
     auto load_meta = [&](int64_t p, MkTileMeta &m) { mk_load_meta(A, p, end, m); };
-    constexpr bool PAT = (FMT == 4);
+    constexpr bool PAT = (FMT == MK_FMT_PAT);
     // ---- windowed tiles with a value dictionary: ROW PHASE ONLY.  One 32-bit word per nonzero {slot | code};
     // the words and the x windows of a tile go straight to LDS with global_load_lds (no VGPR round trip, no
     // per-nonzero staging work); after one barrier lane t walks row t left to right: word, x and value from LDS
@@ -27,8 +27,7 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt24(const MkCsrView &A, const do
     // fmt 2: a tile's packed words behind its windows.  fmt 4: the pattern table, which lives as long as the kernel
     // and therefore sits behind everything the gather path of a tile without windows may overwrite
     // (unless every tile has windows: then the gather path never runs, A.allwin)
-    const int wtop = 128 * A.wchunks + 2;
-    uint32_t *spk = reinterpret_cast<uint32_t *>(xw + ((PAT && !A.allwin && wtop < MK_PROD_LDS) ? MK_PROD_LDS : wtop));
+    uint32_t *spk = reinterpret_cast<uint32_t *>(xw + (PAT ? mk_spmv_wtop(A.wchunks, A.allwin) : 128 * A.wchunks + 2));
     __shared__ double sdict[PAT ? 1 : 256];              // (fmt 4 keeps the values in its pattern table)
     if constexpr (!PAT) sdict[tid] = (tid < A.ndict) ? A.dict[tid] : 0.0;   // (read after a barrier below)
     [[maybe_unused]] __shared__ int splen[PAT ? 256 : 1];

@@ -25,8 +25,7 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt5(const MkCsrView &A, const dou
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     // behind the windows (and whatever the gather path of a tile without windows may overwrite): 256 zeros, then the
     // pattern table -- per entry the byte offset of its x value relative to the lane's own cell
-    const int wtop = 128 * A.wchunks + 2;
-    double *zeros = xw + ((!A.allwin && wtop < MK_PROD_LDS) ? MK_PROD_LDS : wtop);
+    double *zeros = xw + mk_spmv_wtop(A.wchunks, A.allwin);
     int *otab = reinterpret_cast<int *>(zeros + MK_BLOCK);
     const int zoff = (int)((zeros - xw) * (int)sizeof(double));
     zeros[tid] = 0.0;

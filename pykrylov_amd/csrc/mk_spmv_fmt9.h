@@ -101,10 +101,7 @@ __device__ __forceinline__ double mk_pen_term(double s, double v, unsigned m, do
 
 constexpr int MK_PEN_R = 6;                                  // ring slots = unroll factor (own rows: prefetch depth R - 3 planes)
 constexpr int MK_PEN_H = 3;                                  // slots of the halo / pattern-byte rings (depth H planes; R % H == 0)
-constexpr int MK_PEN_OCC = 2;                                // workgroups per CU the register budget is cut for (profiles/r05_pencil_variants.txt)
-constexpr int MK_PEN_RS = 132;                               // LDS row: [0] pad, [1] west edge, [2..129] rows, [130] east edge, [131] pad
-constexpr int MK_PEN_LDS = 3 * 6 * MK_PEN_RS + MK_BLOCK;     // doubles: two plane images of 6 rows + the dump rows (lanes without an
-                                                             // edge row store there, at the same buffer offset as the others)
+// (MK_PEN_OCC, the LDS row MK_PEN_RS and the sizes MK_PEN_LDS, MK_PEN_VB, MK_PEN_LDS_SYM: mk_variant.h)
 
 // SYM (storage format 11): format 10 for matrices that are SYMMETRIC bit for bit -- what CG runs on.  Only the diagonal and the
 // upper offsets (+1, +L, +P) are stored, 32 B per row instead of 56: a(r, r-1) is row r-1's +1 value -- the left lane's, or
@@ -114,9 +111,6 @@ constexpr int MK_PEN_LDS = 3 * 6 * MK_PEN_RS + MK_BLOCK;     // doubles: two pla
 // third stays in two registers.  A lower value is ANDed with the row's presence mask: the product's mask trick needs the VALUE
 // of an absent entry to be +0.0, and a clamped edge load may have fetched a stranger's.  The first plane of a rank's slab
 // takes its -P values (the neighbour's +P values) from an array of one plane behind the four value arrays.
-constexpr int MK_PEN_VB = 6 * 128 + 4 * MK_PEN_RS;           // doubles per buffer of the value image: 5 lines of +L values (halo
-                                                             // line, four brick lines) + a dump line, 4 lines of +1 values
-constexpr int MK_PEN_LDS_SYM = MK_PEN_LDS + 2 * MK_PEN_VB;
 
 // v where the mask is all ones, +0.0 where it is zero
 __device__ __forceinline__ double mk_pen_sel(double v, unsigned m) {

@@ -52,8 +52,7 @@ __device__ __forceinline__ void mk_spmv_tiles_wide(const MkCsrView &A, const dou
     // 256 zeros | windows (or the gather path's products of a tile without windows) | pattern words (mode 1)
     double *zeros = smem;
     double *xw = smem + MK_BLOCK;
-    const int wtop = 128 * A.wchunks + 2;
-    uint32_t *wtab = reinterpret_cast<uint32_t *>(xw + ((!A.allwin && wtop < MK_PROD_LDS) ? MK_PROD_LDS : wtop));
+    uint32_t *wtab = reinterpret_cast<uint32_t *>(xw + mk_spmv_wtop(A.wchunks, A.allwin));
     zeros[tid] = 0.0;
     if constexpr (!DICT) {
         if (mode == 1) {
