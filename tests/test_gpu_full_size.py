@@ -334,7 +334,9 @@ def test_full_runs_against_the_order_independent_anchor():
 def test_non_temporal_accesses_are_the_default_beyond_the_infinity_cache(op512):
     """Value loads of the streaming formats and the CG product's stores go past the caches when a vector is larger than
     256 MiB (mk_stream_nt, csrc/mk_device.h); smaller problems keep their vectors in the caches.  The products above and
-    the CG runs below therefore exercise the non-temporal instantiations at 512^3."""
+    the CG runs below therefore exercise the non-temporal instantiations at 512^3 -- CG's only: the NT variants of every
+    streamed format and the non-temporal stores of the other loops' epilogues are forced on small matrices and compared
+    with the flag off, bit for bit, in tests/test_gpu_nontemporal.py."""
     import ctypes
     from pykrylov_amd import _lib, gallery
     lib = _lib.init()
