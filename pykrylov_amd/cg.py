@@ -56,11 +56,8 @@ class CG(KrylovMethod):
         def prec(r):                                                   # y = precon * r for `store_resids` (cg.py:96,133)
             if pdiag is None:
                 return r
-            if isinstance(pdiag, DevicePrecon):
+            if isinstance(pdiag, (DevicePrecon, HostPrecon)):           # (HostPrecon: the dispatch of the loop's callback)
                 return pdiag.apply(r)
-            if isinstance(pdiag, HostPrecon):                           # (same dispatch as the device loop's callback)
-                p = pdiag.precon
-                return p * r if hasattr(p, '__mul__') else p(r)
             return pdiag * r
 
         with DeviceRun(op, _lib.MK_CG, rhs, guess, precon_diag=pdiag, abstol=float(self.abstol),

@@ -284,7 +284,7 @@ struct BicgstabSolver : mk_solver {
                 (rc = alloc_vec(&d_t, n)))
                 return rc;
         }
-        if (d_prec && !d_q) {
+        if (d_prec() && !d_q) {
             int rc;
             if ((rc = alloc_vec(&d_q, nx)) || (rc = alloc_vec(&d_z, nx))) return rc;
         }
@@ -308,36 +308,36 @@ struct BicgstabSolver : mk_solver {
         // r = r0.copy(); p = v = 0; the first pass's p update (beta p - beta omega v + r) gives exactly r
         mk_launch_stream(this, MkOpCopy{d_r0, d_r}, n);
         mk_launch_stream(this, MkOpCopy{d_r0, d_p}, n);
-        if (d_prec) mk_launch_stream(this, MkOpMul{d_prec, d_r0, d_q}, n);     // q = precon * p   bicgstab.py:96-97
+        if (d_prec()) mk_launch_stream(this, MkOpMul{d_prec(), d_r0, d_q}, n);     // q = precon * p   bicgstab.py:96-97
         if (general_precon() && apply_precon(d_r0, d_q) != MK_OK) return MK_ERR_STATE;
         MK_HIP(hipMemsetAsync(d_v, 0, sizeof(double) * (size_t)n, stream));
         return MK_OK;
     }
 
     int enqueue_spmv_only(int which) override {            // (timing aid: a product's kernel without its gate)
-        if (which == 0) mk_launch_spmv(this, d_prec ? d_q : d_p, BEpi{d_r0, d_v, mk_store_nt(A)}, false);
-        else if (which == 1) mk_launch_spmv(this, d_prec ? d_z : d_s, DEpi{d_s, d_r0, d_t, mk_store_nt(A)}, false);
+        if (which == 0) mk_launch_spmv(this, d_prec() ? d_q : d_p, BEpi{d_r0, d_v, mk_store_nt(A)}, false);
+        else if (which == 1) mk_launch_spmv(this, d_prec() ? d_z : d_s, DEpi{d_s, d_r0, d_t, mk_store_nt(A)}, false);
         else return mk_fail(MK_ERR_ARG, "BiCGSTAB has two products per pass");
         return MK_OK;
     }
 
     int enqueue_pass() override {
         const int par = (int)(it & 1);
-        double *qin = d_prec ? d_q : d_p, *zin = d_prec ? d_z : d_s;           // what the two products read
+        double *qin = d_prec() ? d_q : d_p, *zin = d_prec() ? d_z : d_s;           // what the two products read
         int rc;
         if (general_precon() && it > 0 && (rc = apply_precon(d_p, d_q)) != MK_OK) return rc;   // q = precon * p  bicgstab.py:96-97
         if ((rc = exchange(qin)) != MK_OK) return rc;
         mk_launch_spmv(this, qin, BEpi{d_r0, d_v, mk_store_nt(A)}, true,
                        GateB{d_part, np_stream, d_scal, d_status, it == 0 ? 1 : 0, prm.matvec_max, nmv0 + 2 * it});
         if ((rc = allreduce(SLOT_R0V, 1)) != MK_OK) return rc;
-        mk_launch_stream(this, OpC{d_part, np_spmv, d_scal, par, d_r, d_v, d_s, d_prec, d_z, 0.0}, n);
+        mk_launch_stream(this, OpC{d_part, np_spmv, d_scal, par, d_r, d_v, d_s, d_prec(), d_z, 0.0}, n);
         if ((rc = allreduce(SLOT_SS, 1)) != MK_OK) return rc;
         if (general_precon() && (rc = apply_precon(d_s, d_z)) != MK_OK) return rc;     // z = precon * s       bicgstab.py:120-121
         if ((rc = exchange(zin)) != MK_OK) return rc;
         mk_launch_spmv(this, zin, DEpi{d_s, d_r0, d_t, mk_store_nt(A)}, true,
                        GateD{d_part, np_stream, d_scal, d_status, prm.matvec_max, nmv0 + 2 * it + 1});
         if ((rc = allreduce(SLOT_TS, 3)) != MK_OK) return rc;
-        mk_launch_stream(this, OpF{d_part, np_spmv, d_scal, d_status, par, d_t, d_v, d_s, d_r, d_x, d_p, d_prec, d_q,
+        mk_launch_stream(this, OpF{d_part, np_spmv, d_scal, d_status, par, d_t, d_v, d_s, d_r, d_x, d_p, d_prec(), d_q,
                                    d_z, 0, 0, 0, 0, 0}, n);
         if ((rc = allreduce(SLOT_RR, 1)) != MK_OK) return rc;
         return MK_OK;

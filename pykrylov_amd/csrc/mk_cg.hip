@@ -520,8 +520,8 @@ struct CgSolver : mk_solver {
         } else {
             MK_HIP(hipMemsetAsync(d_x, 0, sizeof(double) * (size_t)nx, stream));
         }
-        if (d_prec) {
-            mk_launch_stream(this, MkOpMul{d_prec, d_r, d_Ap}, n);          // y = precon * r    cg.py:91-92
+        if (d_prec()) {
+            mk_launch_stream(this, MkOpMul{d_prec(), d_r, d_Ap}, n);          // y = precon * r    cg.py:91-92
             if (general_precon() && apply_precon(d_r, d_Ap) != MK_OK) return MK_ERR_STATE;
             mk_launch_stream(this, MkOpDot<1>{d_r, d_Ap}, n);               // ry = <r, y>       cg.py:99
         } else {
@@ -582,7 +582,7 @@ struct CgSolver : mk_solver {
                 launch_fused(pbuf(it - 1), pbuf(it), true);
             }
             if ((rc = allreduce(0, 1)) != MK_OK) return rc;
-            CgUpdateR k2{d_part, np_spmv, d_scal, d_status, par, prm.check_curvature, d_Ap, d_r, d_prec, 0.0, false};
+            CgUpdateR k2{d_part, np_spmv, d_scal, d_status, par, prm.check_curvature, d_Ap, d_r, d_prec(), 0.0, false};
             if (xdefer > 1) k2.aslot = d_scal + S_ARING + (int)(it % (xdefer + 1));
             mk_launch_stream(this, k2, n);
             if ((rc = allreduce(1, 1)) != MK_OK) return rc;
@@ -599,7 +599,7 @@ struct CgSolver : mk_solver {
         else mk_launch_spmv(this, d_p, CgSpmvEpi{d_p, d_Ap, 0.0});
         if ((rc = allreduce(0, 1)) != MK_OK) return rc;
         mk_launch_stream(this, CgUpdateR{d_part, np_spmv, d_scal, d_status, par, prm.check_curvature, d_Ap, d_r,
-                                         d_prec, 0.0, false}, n);
+                                         d_prec(), 0.0, false}, n);
         if (general_precon()) {                             // y = precon * r ; <r, y> re-formed   cg.py:137-138,146
             if ((rc = apply_precon(d_r, d_Ap)) != MK_OK) return rc;
             mk_launch_stream(this, MkOpDot<1>{d_r, d_Ap}, n);

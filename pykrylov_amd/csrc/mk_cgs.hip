@@ -220,7 +220,7 @@ struct CgsSolver : mk_solver {
                 (rc = alloc_vec(&d_v, n)) || (rc = alloc_vec(&d_z, nx)))
                 return rc;
         }
-        if (d_prec && !d_y) {
+        if (d_prec() && !d_y) {
             int rc = alloc_vec(&d_y, nx);
             if (rc) return rc;
         }
@@ -242,13 +242,13 @@ struct CgsSolver : mk_solver {
         mk_launch_stream(this, MkOpCopy{d_r0, d_r}, n);                        // r = r0.copy()    cgs.py:72
         mk_launch_stream(this, MkOpCopy{d_r0, d_u}, n);                        // u = r0           cgs.py:73
         mk_launch_stream(this, MkOpCopy{d_r0, d_p}, n);                        // p = r0.copy()    cgs.py:74
-        if (d_prec) mk_launch_stream(this, MkOpMul{d_prec, d_r0, d_y}, n);     // y = precon * p   cgs.py:79-80
+        if (d_prec()) mk_launch_stream(this, MkOpMul{d_prec(), d_r0, d_y}, n);     // y = precon * p   cgs.py:79-80
         if (general_precon() && (rc = apply_precon(d_p, d_y)) != MK_OK) return rc;
         return MK_OK;
     }
 
     int enqueue_spmv_only(int which) override {            // (timing aid: a product's kernel without its gate)
-        if (which == 0) mk_launch_spmv(this, d_prec ? d_y : d_p, BEpi{d_r0, d_v, mk_store_nt(A)}, false);
+        if (which == 0) mk_launch_spmv(this, d_prec() ? d_y : d_p, BEpi{d_r0, d_v, mk_store_nt(A)}, false);
         else if (which == 1) mk_launch_spmv(this, d_z, DEpi{d_scal, d_r0, d_r, 0.0}, false);
         else return mk_fail(MK_ERR_ARG, "CGS has two products per pass");
         return MK_OK;
@@ -256,13 +256,13 @@ struct CgsSolver : mk_solver {
 
     int enqueue_pass() override {
         const int par = (int)(it & 1);
-        double *yin = d_prec ? d_y : d_p;
+        double *yin = d_prec() ? d_y : d_p;
         int rc;
         if (general_precon() && it > 0 && (rc = apply_precon(d_p, d_y)) != MK_OK) return rc;   // y = precon * p   cgs.py:79-80
         if ((rc = exchange(yin)) != MK_OK) return rc;
         mk_launch_spmv(this, yin, BEpi{d_r0, d_v, mk_store_nt(A)}, true, CountGate{d_status, 2 * it});
         if ((rc = allreduce(SLOT_SIGMA, 1)) != MK_OK) return rc;
-        mk_launch_stream(this, OpC{d_part, np_spmv, d_scal, par, d_u, d_v, d_q, d_z, d_x, d_prec, 0.0, general_precon() ? 1 : 0}, n);
+        mk_launch_stream(this, OpC{d_part, np_spmv, d_scal, par, d_u, d_v, d_q, d_z, d_x, d_prec(), 0.0, general_precon() ? 1 : 0}, n);
         if (general_precon()) {                             // z = precon * (u + q) ; x += alpha z     cgs.py:88-94
             if ((rc = apply_precon(d_z, d_z)) != MK_OK) return rc;
             mk_launch_stream(this, OpXZ{d_scal, d_z, d_x, 0.0}, n);
@@ -271,7 +271,7 @@ struct CgsSolver : mk_solver {
         mk_launch_spmv(this, d_z, DEpi{d_scal, d_r0, d_r, 0.0}, true, CountGate{d_status, 2 * it + 1});
         if ((rc = allreduce(SLOT_RR, 2)) != MK_OK) return rc;
         mk_launch_stream(this, OpF{d_part, np_spmv, d_scal, d_status, par, prm.matvec_max, 2 * it + 2, d_r, d_q, d_u,
-                                   d_p, d_prec, d_y, 0.0, false}, n);
+                                   d_p, d_prec(), d_y, 0.0, false}, n);
         return MK_OK;
     }
 

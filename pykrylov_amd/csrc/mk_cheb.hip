@@ -330,9 +330,9 @@ extern "C" int mk_cheb_coefficients(const mk_cheb *F, double *host) {
 }
 
 extern "C" int mk_solver_set_precon_cheb(mk_solver *s, const mk_cheb *F) {
-    return mk_set_precon_object(s, F, "mk_solver_set_precon_cheb", "Chebyshev preconditioner", "Chebyshev preconditioners");
+    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_cheb", "Chebyshev preconditioner");
 }
 
 extern "C" int mk_solver_set_lls_precon_cheb(mk_solver *s, int side, const mk_cheb *F) {
-    return mk_lls_set_precon_object(s, side, F, "mk_solver_set_lls_precon_cheb", "Chebyshev preconditioner");
+    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_cheb", "Chebyshev preconditioner");
 }

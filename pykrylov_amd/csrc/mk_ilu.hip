@@ -390,11 +390,11 @@ extern "C" int mk_ilu_destroy(mk_ilu *F) {
 }
 
 extern "C" int mk_solver_set_precon_ilu(mk_solver *s, const mk_ilu *F) {
-    return mk_set_precon_object(s, F, "mk_solver_set_precon_ilu", "factor", "incomplete factorizations");
+    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_ilu", "incomplete factorization");
 }
 
 extern "C" int mk_solver_set_lls_precon_ilu(mk_solver *s, int side, const mk_ilu *F) {
-    return mk_lls_set_precon_object(s, side, F, "mk_solver_set_lls_precon_ilu", "factor");
+    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_ilu", "incomplete factorization");
 }
 
 extern "C" int mk_ilu_apply(const mk_ilu *F, const double *in_dev, double *out_dev) {

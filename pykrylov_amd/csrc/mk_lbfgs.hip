@@ -417,11 +417,11 @@ extern "C" int mk_lbfgs_destroy(mk_lbfgs *F) {
 }
 
 extern "C" int mk_solver_set_precon_lbfgs(mk_solver *s, const mk_lbfgs *F) {
-    return mk_set_precon_object(s, F, "mk_solver_set_precon_lbfgs", "operator", "L-BFGS operators");
+    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_lbfgs", "L-BFGS operator");
 }
 
 extern "C" int mk_solver_set_lls_precon_bfgs(mk_solver *s, int side, const mk_lbfgs *F) {
-    return mk_lls_set_precon_object(s, side, F, "mk_solver_set_lls_precon_bfgs", "operator");
+    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_bfgs", "L-BFGS operator");
 }
 
 extern "C" int mk_lbfgs_store(mk_lbfgs *F, const double *s_dev, const double *y_dev, double threshold, int32_t *accepted) {

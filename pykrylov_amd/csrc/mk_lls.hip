@@ -1004,10 +1004,6 @@ struct OpInitM {     // CRAIG: d = u / rho ; r = tau d.  CRAIG-MR: d = u / alpha
     __device__ void one(int64_t i, double *) { elem(i); }
 };
 
-__global__ __launch_bounds__(MK_BLOCK) void lls_fill_kernel(double *v, int64_t n, double a) {
-    for (int64_t i = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MK_BLOCK) v[i] = a;
-}
-
 struct LlsSolver : mk_solver {
     int kind;
     int64_t m = 0, nn = 0, nF = 0;
@@ -1015,29 +1011,21 @@ struct LlsSolver : mk_solver {
     double *d_a = nullptr, *d_b = nullptr;      // LSQR: w ; LSMR: h, hbar ; CRAIG: w, wbar
     double *d_d = nullptr, *d_r = nullptr, *d_dbar = nullptr;
     double *d_Mu = nullptr, *d_Nv = nullptr;     // only with preconditioners
-    const double *d_dm = nullptr, *d_dn = nullptr; // diagonals of M (m entries) and N (n entries), borrowed
     int np_A = 1, np_At = 1, np_n = 1, np_m = 1;
     int64_t itnlim = 0;
-    // M and N (mk_solver_set_lls_precon*): a diagonal is multiplied inside the kernels (d_dm / d_dn).  With a general kind
-    // the kernels run with a diagonal of ones and `u = M(Mu)` / `v = N(Nv)` is replaced by mk_solver::apply_slot's result
-    // right after the kernel that formed Mu / Nv; <u, Mu> / <v, Nv> are then re-formed in the stream kernels' order
-    MkPrecon pm, pn;
-    double *d_ones_m = nullptr, *d_ones_n = nullptr;
+    // M and N (mk_solver_set_lls_precon*) are the base's two slots; the loop only reads them.  A diagonal is multiplied
+    // inside the kernels (M().d / N().d).  With a general kind the kernels run with a diagonal of ones and `u = M(Mu)` /
+    // `v = N(Nv)` is replaced by mk_solver::apply_slot's result right after the kernel that formed Mu / Nv; <u, Mu> /
+    // <v, Nv> are then re-formed in the stream kernels' order
+    const MkPrecon &M() const { return slot[MK_LLS_SIDE_M]; }
+    const MkPrecon &N() const { return slot[MK_LLS_SIDE_N]; }
     double *d_ntmp = nullptr;                    // N(Nv) of a device object before it is taken (OpTakeV)
 
-    ~LlsSolver() override {
-        if (mk_ctx().ready) hipStreamSynchronize(mk_ctx().stream);   // (an object released below may free its memory)
-        pm.release();
-        pn.release();
-        hipFree(d_ones_m);
-        hipFree(d_ones_n);
-    }
-
     // <v, Nv> comes from the A' product's epilogue, or from the stream kernel that follows a general N
-    int np_vv() const { return pn.general() ? np_n : np_At; }
+    int np_vv() const { return N().general() ? np_n : np_At; }
     int apply_M(bool force) {                    // u = M(Mu) ; <u, Mu>
-        if (!pm.general()) return MK_OK;
-        int rc = apply_slot(pm, m, d_Mu, d_u, force);
+        if (!M().general()) return MK_OK;
+        int rc = apply_slot(M(), d_Mu, d_u, force);
         if (rc != MK_OK) return rc;
         mk_launch_stream(this, MkOpDot<SLOT_UU>{d_u, d_Mu}, m);
         return MK_OK;
@@ -1046,48 +1034,19 @@ struct LlsSolver : mk_solver {
     // rescaled since v was formed).  A callback reads beta with the halt word; a device matrix is multiplied under the A'
     // product's own gate, straight into v; a device object's result is taken by OpTakeV.
     int apply_N(bool force) {
-        if (!pn.general()) return MK_OK;
-        if (pn.kind == MK_PRECON_OBJECT) {
-            int rc = apply_slot(pn, nn, d_Nv, d_ntmp, force);
+        if (!N().general()) return MK_OK;
+        if (N().kind == MK_PRECON_OBJECT) {
+            int rc = apply_slot(N(), d_Nv, d_ntmp, force);
             if (rc != MK_OK) return rc;
             mk_launch_stream(this, OpTakeV{d_scal, d_ntmp, d_Nv, d_v, false}, nn);
             return MK_OK;
         }
-        int rc = pn.kind == MK_PRECON_CSR ? mk_apply_csr_slot(this, pn.op, nn, d_Nv, d_v, force, GateV{d_scal})
-                                          : apply_slot(pn, nn, d_Nv, d_v, force, d_scal + S_BETA);
+        int rc = N().kind == MK_PRECON_CSR ? mk_apply_csr_slot(this, N(), d_Nv, d_v, force, GateV{d_scal})
+                                          : apply_slot(N(), d_Nv, d_v, force, d_scal + S_BETA);
         if (rc != MK_OK) return rc;
         mk_launch_stream(this, MkOpDot<SLOT_VV>{d_v, d_Nv}, nn);
         return MK_OK;
     }
-    int set_side(int side, const MkPrecon &next, const double *diag, const char *who, const char *noun) {
-        MkPrecon &slot = side ? pn : pm;
-        const double *&dd = side ? d_dn : d_dm;
-        double *&ones = side ? d_ones_n : d_ones_m;
-        const int64_t mm = A->nrows, nc = A->ncols, len = side ? nc : mm, cap = mm > nc ? mm : nc;
-        const char *name = side ? "N" : "M";
-        if (next.kind == MK_PRECON_OBJECT && next.obj->n != len)
-            return mk_fail(MK_ERR_ARG, "%s: the %s has %lld rows, %s takes vectors of %lld entries", who, noun,
-                           (long long)next.obj->n, name, (long long)len);
-        if (next.kind == MK_PRECON_CSR && (next.op->nrows != len || next.op->ncols != len || next.op->ex.mode >= 0))
-            return mk_fail(MK_ERR_ARG, "%s: %s must be a square device operator of size %lld without an exchange plan, got "
-                           "%lld x %lld", who, name, (long long)len, (long long)next.op->nrows, (long long)next.op->ncols);
-        if (next.general() && !ones) {
-            MK_HIP(hipMalloc((void **)&ones, sizeof(double) * (size_t)(len > 0 ? len : 1) + 16));
-            hipLaunchKernelGGL(lls_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, stream, ones, len, 1.0);
-            MK_HIP(hipGetLastError());
-        }
-        if (next.kind == MK_PRECON_HOST && !h_pin) {         // (one pair of pinned buffers serves both sides)
-            MK_HIP(hipHostMalloc((void **)&h_pin, sizeof(double) * (size_t)(cap > 0 ? cap : 1), hipHostMallocDefault));
-            MK_HIP(hipHostMalloc((void **)&h_pout, sizeof(double) * (size_t)(cap > 0 ? cap : 1), hipHostMallocDefault));
-        }
-        // take the new reference first, then drop the old one: re-setting the attached object must not free it
-        next.hold();
-        slot.release();
-        slot = next;
-        dd = next.general() ? ones : (next.kind == MK_PRECON_DIAG ? diag : nullptr);
-        return MK_OK;
-    }
-
     // several GPUs, A = this rank's row block (mk_csr_set_row_block): m-space vectors are slices; n-space vectors are
     // either whole and identical on every rank (mode 1: A' u is all-reduced, all n-space work replicated -- fine for
     // m >> n) or SLICED (mode 2): rank r owns entries [r cnt, (r + 1) cnt) of every n-space vector, A' u is
@@ -1100,7 +1059,7 @@ struct LlsSolver : mk_solver {
     int64_t cnt = 0, off = 0, nl = 0;            // sliced: entries per rank, this rank's offset, its real entries
     // n-space operands as the kernels see them: the whole vector, or this rank's slice
     double *vL() const { return d_v + off; }
-    const double *dnL() const { return d_dn ? d_dn + off : nullptr; }
+    const double *dnL() const { return N().d ? N().d + off : nullptr; }
     int gather_v() { return sliced ? mk_comm_allgather(vL(), d_v, cnt, stream) : (int)MK_OK; }
     // (only LSQR's ||dk||^2 and LSMR's ||x||^2 live in SLOT_X: the CRAIG kernels produce no such partial sums)
     int sum_x() { return (sliced && (kind == MK_LSQR || kind == MK_LSMR)) ? allreduce(SLOT_X, 1) : (int)MK_OK; }
@@ -1110,7 +1069,7 @@ struct LlsSolver : mk_solver {
     // G3: v <- A' u - beta v with <v, v>
     int product_At(bool in_setup) {
         if (!dist) {
-            mk_launch_spmv_on(this, At, d_u, EpiV{d_scal, d_v, d_dn, d_Nv, 0.0}, GateV{d_scal});
+            mk_launch_spmv_on(this, At, d_u, EpiV{d_scal, d_v, N().d, d_Nv, 0.0}, GateV{d_scal});
             return apply_N(in_setup);
         }
         mk_launch_spmv_on(this, At, d_u, MkPlainEpi{d_t}, GateV{d_scal});
@@ -1122,7 +1081,7 @@ struct LlsSolver : mk_solver {
         }
         int rc = mk_comm_allreduce_sum(d_t, nn, stream);   // (a skipped product leaves old data: OpVt skips as well)
         if (rc != MK_OK) return rc;
-        mk_launch_stream(this, OpVt{d_scal, d_t, d_v, d_dn, d_Nv, 0.0}, nn);
+        mk_launch_stream(this, OpVt{d_scal, d_t, d_v, N().d, d_Nv, 0.0}, nn);
         return MK_OK;
     }
 
@@ -1136,7 +1095,7 @@ struct LlsSolver : mk_solver {
                            "not with a halo / all-gather exchange plan");
         dist = A->row_block && mk_comm_active();
         sliced = dist && A->row_block == 2;
-        if (dist && (A->host_fn || At->host_fn || pm.general() || pn.general()))
+        if (dist && (A->host_fn || At->host_fn || M().general() || N().general()))
             return mk_fail(MK_ERR_UNSUPPORTED, "least-squares solvers: matrix-free operators and M / N other than "
                            "diagonals are single-GPU");
         if (prm.window < 1 || prm.window > MAXWIN) return mk_fail(MK_ERR_ARG, "window must be in 1..%d", MAXWIN);
@@ -1179,15 +1138,15 @@ struct LlsSolver : mk_solver {
         for (double *p : {d_d, d_r, d_dbar}) MK_HIP(hipMemsetAsync(p, 0, sizeof(double) * (size_t)m, stream));
         MK_HIP(hipMemsetAsync(d_x, 0, sizeof(double) * (size_t)(kind == MK_CRAIGMR ? m : nA), stream));
         int rc2;
-        if (d_dm && !d_Mu && (rc2 = alloc_vec(&d_Mu, m))) return rc2;
-        if (d_dn && !d_Nv && (rc2 = alloc_vec(&d_Nv, nA))) return rc2;
-        if (pn.kind == MK_PRECON_OBJECT && !d_ntmp && (rc2 = alloc_vec(&d_ntmp, nn))) return rc2;
+        if (M().d && !d_Mu && (rc2 = alloc_vec(&d_Mu, m))) return rc2;
+        if (N().d && !d_Nv && (rc2 = alloc_vec(&d_Nv, nA))) return rc2;
+        if (N().kind == MK_PRECON_OBJECT && !d_ntmp && (rc2 = alloc_vec(&d_ntmp, nn))) return rc2;
         if (dist && !d_t && (rc2 = alloc_vec(&d_t, nF))) return rc2;          // (entries past nn stay zero)
         if (sliced && !d_tl && ((rc2 = alloc_vec(&d_tl, cnt)) || (rc2 = alloc_vec(&d_xfull, nF)))) return rc2;
         if (d_Nv) MK_HIP(hipMemsetAsync(d_Nv, 0, sizeof(double) * (size_t)nA, stream));
-        if (d_dm) {
+        if (M().d) {
             mk_launch_stream(this, MkOpCopy{rhs, d_Mu}, m);                            // Mu = rhs.copy()   lsqr.py:188
-            mk_launch_stream(this, MkOpMul{d_dm, d_Mu, d_u}, m);                       // u = M(Mu)         lsqr.py:190
+            mk_launch_stream(this, MkOpMul{M().d, d_Mu, d_u}, m);                       // u = M(Mu)         lsqr.py:190
             mk_launch_stream(this, MkOpDot<SLOT_UU>{d_u, d_Mu}, m);                    // <u, Mu>           lsqr.py:195
             if ((rc2 = apply_M(true)) != MK_OK) return rc2;
         } else {
@@ -1195,14 +1154,14 @@ struct LlsSolver : mk_solver {
             mk_launch_stream(this, MkOpDot<SLOT_UU>{d_u, d_u}, m);                     // lsqr.py:195
         }
         if ((rc2 = sum_uu()) != MK_OK) return rc2;
-        mk_launch_stream(this, OpNormU{d_part, np_m, d_scal, d_u, d_dm ? d_Mu : nullptr, 0.0}, m);   // lsqr.py:197-198
+        mk_launch_stream(this, OpNormU{d_part, np_m, d_scal, d_u, M().d ? d_Mu : nullptr, 0.0}, m);   // lsqr.py:197-198
         // Nv = A' u (Nv is zero: the epilogue's "- beta Nv" term vanishes exactly)     lsqr.py:200
         if ((rc2 = product_At(true)) != MK_OK) return rc2;
         hipLaunchKernelGGL(lls_init_kernel, dim3(1), dim3(MK_BLOCK), 0, stream, d_part, np_vv(), d_scal, d_status,
                            next_halt(), kind, itnlim);
         mk_launch_stream(this, OpInitN{d_scal, kind, vL(), d_a, d_b, d_x, 0, 0, 0, 0}, nl);
         if ((rc2 = gather_v()) != MK_OK) return rc2;
-        if (d_dn) mk_launch_stream(this, OpScaleNv{d_scal, d_scal + S_BLK, 0, d_Nv, 0.0, false}, nl);   // lsqr.py:209
+        if (N().d) mk_launch_stream(this, OpScaleNv{d_scal, d_scal + S_BLK, 0, d_Nv, 0.0, false}, nl);   // lsqr.py:209
         if (kind == MK_CRAIG || kind == MK_CRAIGMR)
             mk_launch_stream(this, OpInitM{d_scal, kind, d_u, d_d, d_r, 0, 0}, m);
         return MK_OK;
@@ -1211,8 +1170,8 @@ struct LlsSolver : mk_solver {
     int enqueue_spmv_only(int which) override {            // (timing aid: a product's kernel without its gate; one GPU)
         if (dist) return mk_fail(MK_ERR_UNSUPPORTED, "product timing of the least-squares solvers is single-GPU");
         const double *blk = d_scal + S_BLK + (int)(it & 1) * BLK;
-        if (which == 0) mk_launch_spmv_on(this, A, d_v, EpiU{blk, d_u, d_dm, d_Mu, 0.0, mk_store_nt(A)});
-        else if (which == 1) mk_launch_spmv_on(this, At, d_u, EpiV{d_scal, d_v, d_dn, d_Nv, 0.0});
+        if (which == 0) mk_launch_spmv_on(this, A, d_v, EpiU{blk, d_u, M().d, d_Mu, 0.0, mk_store_nt(A)});
+        else if (which == 1) mk_launch_spmv_on(this, At, d_u, EpiV{d_scal, d_v, N().d, d_Nv, 0.0});
         else return mk_fail(MK_ERR_ARG, "the least-squares solvers have two products per pass (A v, A' u)");
         return MK_OK;
     }
@@ -1224,18 +1183,18 @@ struct LlsSolver : mk_solver {
         const int64_t itn = it + 1;
         // G1: u <- A v - alpha u, gated by what is left of the previous pass
         if (kind == MK_LSQR)
-            mk_launch_spmv_on(this, A, d_v, EpiU{blk, d_u, d_dm, d_Mu, 0.0, mk_store_nt(A)},
+            mk_launch_spmv_on(this, A, d_v, EpiU{blk, d_u, M().d, d_Mu, 0.0, mk_store_nt(A)},
                               lsqr::Gate{d_part, np_n, d_scal, d_status, it, itnlim, prm.atol});
         else if (kind == MK_LSMR)
-            mk_launch_spmv_on(this, A, d_v, EpiU{blk, d_u, d_dm, d_Mu, 0.0, mk_store_nt(A)},
+            mk_launch_spmv_on(this, A, d_v, EpiU{blk, d_u, M().d, d_Mu, 0.0, mk_store_nt(A)},
                               lsmr::Gate{d_part, np_n, d_scal, d_status, it, itnlim, prm.atol, prm.btol,
                                          prm.conlim > 0 ? 1.0 / prm.conlim : 0.0});
         else
-            mk_launch_spmv_on(this, A, d_v, EpiU{blk, d_u, d_dm, d_Mu, 0.0, mk_store_nt(A)}, craig::CountGate{d_status, it, itnlim});
+            mk_launch_spmv_on(this, A, d_v, EpiU{blk, d_u, M().d, d_Mu, 0.0, mk_store_nt(A)}, craig::CountGate{d_status, it, itnlim});
         int rc = apply_M(false);
         if (rc != MK_OK) return rc;
         if ((rc = sum_uu()) != MK_OK) return rc;
-        mk_launch_stream(this, OpNormU{d_part, pm.general() ? np_m : np_A, d_scal, d_u, d_dm ? d_Mu : nullptr, 0.0}, m);   // G2
+        mk_launch_stream(this, OpNormU{d_part, M().general() ? np_m : np_A, d_scal, d_u, M().d ? d_Mu : nullptr, 0.0}, m);   // G2
         if ((rc = product_At(false)) != MK_OK) return rc;                                                // G3
         if (kind == MK_LSQR) {
             mk_launch_stream(this, lsqr::OpN{d_part, np_vv(), d_scal, d_status, d_hist, par, itn, prm.window, prm.damp,
@@ -1252,7 +1211,7 @@ struct LlsSolver : mk_solver {
                                                 prm.etol, vL(), 0, false}, nl);
             mk_launch_stream(this, craig::OpMmr{blk_next, d_u, d_d, d_dbar, d_x, 0, 0, 0, 0, 0}, m);
         }
-        if (d_dn) mk_launch_stream(this, OpScaleNv{d_scal, blk_next, 1, d_Nv, 0.0, false}, nl);          // lsqr.py:272
+        if (N().d) mk_launch_stream(this, OpScaleNv{d_scal, blk_next, 1, d_Nv, 0.0, false}, nl);          // lsqr.py:272
         if ((rc = sum_x()) != MK_OK) return rc;              // (sliced: ||dk||^2 / ||x||^2 partials of the slices)
         return gather_v();                                   // ... and the next A v reads v whole
     }
@@ -1291,12 +1250,3 @@ struct LlsSolver : mk_solver {
 }  // namespace
 
 mk_solver *mk_make_lls(int kind) { return new LlsSolver(kind); }
-
-int mk_lls_set_side(mk_solver *s, int side, const MkPrecon &next, const double *diag, const char *who, const char *noun) {
-    return static_cast<LlsSolver *>(s)->set_side(side, next, diag, who, noun);
-}
-
-int mk_lls_side_kind(const mk_solver *s, int side) {
-    const LlsSolver *l = static_cast<const LlsSolver *>(s);
-    return side ? l->pn.kind : l->pm.kind;
-}

@@ -346,9 +346,9 @@ struct MinresSolver : mk_solver {
         for (int k = 0; k < 3; ++k) MK_HIP(hipMemsetAsync(d_w[k], 0, sizeof(double) * (size_t)n, stream));
         mk_launch_stream(this, MkOpCopy{rhs, d_r[0]}, n);                      // r1 = b            minres.py:161
         mk_launch_stream(this, MkOpCopy{rhs, d_r[1]}, n);                      // y = r2 = b.copy() minres.py:165,208
-        if (d_prec) {
+        if (d_prec()) {
             if (!d_y && (rc0 = alloc_vec(&d_y, nx))) return rc0;
-            mk_launch_stream(this, MkOpMul{d_prec, d_r[0], d_y}, n);           // y = precon * b    minres.py:162-163
+            mk_launch_stream(this, MkOpMul{d_prec(), d_r[0], d_y}, n);           // y = precon * b    minres.py:162-163
             if (general_precon() && apply_precon(d_r[0], d_y) != MK_OK) return MK_ERR_STATE;
             mk_launch_stream(this, MkOpDot<SLOT_YY>{d_r[0], d_y}, n);          // beta1 = <b, y>    minres.py:166
         } else {
@@ -366,7 +366,7 @@ struct MinresSolver : mk_solver {
         const int par = (int)(it & 1);                     //  writes v and t of the current pass, which the next pass
         const double *blk = d_scal + S_BLK + par * BLK;    //  overwrites anyway)
         double *r1 = d_r[it & 1], *r2 = d_r[(it + 1) & 1];
-        mk_launch_spmv(this, d_prec ? d_y : r2, EpiK1{blk, d_prec ? d_y : r2, r1, d_v, d_t, prm.shift, 0, 0.0, 0.0, mk_store_nt(A)}, false);
+        mk_launch_spmv(this, d_prec() ? d_y : r2, EpiK1{blk, d_prec() ? d_y : r2, r1, d_v, d_t, prm.shift, 0, 0.0, 0.0, mk_store_nt(A)}, false);
         return MK_OK;
     }
 
@@ -378,13 +378,13 @@ struct MinresSolver : mk_solver {
         // (w1, w2, w) <- (w2, w, new): the new vector overwrites the storage of the vector that was w1 ... two
         // passes ago; at pass `it` the roles are w1 = d_w[it%3] (dead after this pass), w2, and the current w.
         // The reference reads w1 := old w2 and w2 := old w; see below.
-        double *y = d_prec ? d_y : r2;                                         // minres.py:249
+        double *y = d_prec() ? d_y : r2;                                         // minres.py:249
         int rc = exchange(y);
         if (rc != MK_OK) return rc;
         mk_launch_spmv(this, y, EpiK1{blk, y, r1, d_v, d_t, prm.shift, it == 0 ? 1 : 0, 0.0, 0.0, mk_store_nt(A)}, true,
                        GateK1{d_status, it, prm.itnlim});
         if ((rc = allreduce(SLOT_ALFA, 1)) != MK_OK) return rc;
-        mk_launch_stream(this, OpK2{d_part, np_spmv, d_scal, blk, r2, d_t, r1, d_prec, d_y, 0.0}, n);
+        mk_launch_stream(this, OpK2{d_part, np_spmv, d_scal, blk, r2, d_t, r1, d_prec(), d_y, 0.0}, n);
         if (general_precon()) {                             // y = precon * r2 ; <r2, y> re-formed   minres.py:249-251
             if ((rc = apply_precon(r1, d_y)) != MK_OK) return rc;          // (OpK2 wrote the new r2 into r1's storage)
             mk_launch_stream(this, MkOpDot<SLOT_YY>{r1, d_y}, n);

@@ -51,14 +51,14 @@ struct MkDeviceOp {
     }
 };
 
-// A preconditioner slot: the one a square solver carries (mk_solver::precon), and each of M and N of a least-squares solver
-// (mk_lls.hip).  A diagonal is multiplied inside the loop's kernels (mk_solver::d_prec; d_dm / d_dn).  With one of the
-// general kinds the kernels run with a diagonal of ones (`1.0 * v` is exact) and every preconditioned vector is replaced
-// by `apply_slot`'s result right after the kernel that produced it; inner products with it are re-formed by a separate
-// stream kernel.
+// A preconditioner slot.  A solver has two (mk_solver::slot): a square solver uses the first, a least-squares solver both,
+// for M (nrows(A) entries) and N (ncols(A) entries).  A diagonal is multiplied inside the loop's kernels (`d`).  With one of
+// the general kinds the kernels run with a diagonal of ones (`1.0 * v` is exact) and every preconditioned vector is
+// replaced by `apply_slot`'s result right after the kernel that produced it; inner products with it are re-formed by a
+// separate stream kernel.
 enum MkPreconKind {
     MK_PRECON_NONE = 0,
-    MK_PRECON_DIAG,        // mk_solver_set_precon_diag / _lls_precon: the borrowed diagonal is d_prec (d_dm, d_dn) itself
+    MK_PRECON_DIAG,        // mk_solver_set_precon_diag / _lls_precon: the borrowed diagonal is `d` itself
     MK_PRECON_HOST,        // mk_solver_set_precon_callback / _lls_precon_callback: `fn(user, in, out)` on the host, through
                            // pinned buffers
     MK_PRECON_CSR,         // mk_solver_set_precon_csr / _lls_precon_csr: a device matrix or composite `op` (counted in
@@ -68,40 +68,69 @@ enum MkPreconKind {
 };
 
 struct MkPrecon {
+    // what is attached (all that a replacement carries)
     MkPreconKind kind = MK_PRECON_NONE;
     mk_precon_fn fn = nullptr;
     void *user = nullptr;
     const mk_csr *op = nullptr;
     const MkDeviceOp *obj = nullptr;
+    const double *d = nullptr;      // what the kernels multiply by: the borrowed diagonal, `ones` for a general kind, or null
+    // the slot's own, from the solver's creation to its end
+    int64_t len = 0;                // entries of the vectors it takes
+    double *ones = nullptr;         // (owned, allocated with the first general kind)
     bool general() const { return kind >= MK_PRECON_HOST; }
     void hold() const;              // take the reference a slot keeps on a device matrix or object
     void release();                 // drop it and go back to MK_PRECON_NONE
+    // the replacements the setters hand to mk_set_precon; a null argument gives MK_PRECON_NONE
+    static MkPrecon diagonal(const double *diag) {
+        MkPrecon p;
+        if (diag) p.kind = MK_PRECON_DIAG;
+        p.d = diag;
+        return p;
+    }
+    static MkPrecon callback(mk_precon_fn fn, void *user) {
+        MkPrecon p;
+        if (fn) p.kind = MK_PRECON_HOST;
+        p.fn = fn;
+        p.user = user;
+        return p;
+    }
+    static MkPrecon matrix(const mk_csr *op) {
+        MkPrecon p;
+        if (op) p.kind = MK_PRECON_CSR;
+        p.op = op;
+        return p;
+    }
+    static MkPrecon object(const MkDeviceOp *obj) {
+        MkPrecon p;
+        if (obj) p.kind = MK_PRECON_OBJECT;
+        p.obj = obj;
+        return p;
+    }
 };
 
 struct mk_solver {
     const mk_csr *A = nullptr;
     const mk_csr *At = nullptr;     // transposed matrix (least-squares solvers only)
-    MkPrecon precon;
-    const double *d_prec = nullptr; // what the kernels multiply by: the diagonal (n entries), d_ones for a general kind, or null
-    double *d_ones = nullptr;       // (owned, allocated with the first general preconditioner)
-    double *h_pin = nullptr, *h_pout = nullptr;   // pinned staging of the host callback (least squares: max(m, n) entries)
+    MkPrecon slot[2];               // [0]: a square solver's preconditioner, or M of a least-squares one; [1]: N
+    double *h_pin = nullptr, *h_pout = nullptr;   // pinned staging of the host callback, shared by the slots (max of their lengths)
     double *d_ptmp = nullptr;       // product target when a site preconditions a vector in place by a device matrix
     int *d_nohalt = nullptr;        // two zero words: the halt input of a kernel that must run after the loop has ended
-    bool general_precon() const { return precon.general(); }
-    // `next` (a general kind) replaces whatever is attached; the messages name the entry point `who`, and for an object what
-    // it is (`noun`, `plural`)
-    int attach_precon(const MkPrecon &next, const char *who, const char *noun = nullptr, const char *plural = nullptr);
-    void clear_precon();            // back to MK_PRECON_NONE: the only place a preconditioner's reference is released
+    // the square solvers' view of their one slot
+    const double *d_prec() const { return slot[0].d; }
+    bool general_precon() const { return slot[0].general(); }
+    // `next` replaces whatever `into` (one of `slot`) holds; MK_PRECON_NONE leaves it empty.  The messages name the entry
+    // point `who`, the slot (`name`: "the preconditioner", "M", "N") and, for an object, what it is (`noun`).  The one place
+    // that validates a replacement, gives a slot its ones and the solver its pinned buffers, and moves a reference.
+    int attach(MkPrecon &into, const MkPrecon &next, const char *who, const char *name, const char *noun);
     int apply_precon(const double *in_dev, double *out_dev, bool force = false) {   // out = precon * in ; unless `force`, a no-op once the loop has halted
-        return apply_slot(precon, n, in_dev, out_dev, force);
+        return apply_slot(slot[0], in_dev, out_dev, force);
     }
-    // out = slot * in for a general kind on vectors of `len` entries: the square solvers' `precon` and the two slots of the
-    // least-squares solvers (mk_lls.hip).  `need_pos` (least squares, beta of lsqr.py:258): a device scalar that must be
+    // out = slot * in for a general kind.  `need_pos` (least squares, beta of lsqr.py:258): a device scalar that must be
     // > 0 for a HOST callback to run, read with the halt word in the one synchronisation; the launches of the device kinds
     // cannot be gated from the host -- their caller gates the product itself (mk_apply_csr_slot) or takes an out-of-place
     // result on the device
-    int apply_slot(const MkPrecon &slot, int64_t len, const double *in_dev, double *out_dev, bool force,
-                   const double *need_pos = nullptr);
+    int apply_slot(const MkPrecon &slot, const double *in_dev, double *out_dev, bool force, const double *need_pos = nullptr);
     mk_params prm{};
     int64_t n = 0;        // local rows = length of every solver vector
     int64_t nx = 0;       // length of vectors that feed an SpMV (n + halo)
@@ -167,8 +196,9 @@ struct mk_solver {
     int collect_spmv_timing();
 };
 
-// attach a device object as `s`'s preconditioner (F null: none); `who`, `noun`, `plural` as in mk_solver::attach_precon
-int mk_set_precon_object(mk_solver *s, const MkDeviceOp *F, const char *who, const char *noun, const char *plural);
+// Where every extern "C" setter ends: `next` into the slot of a square solver (`side` < 0; refused if the solver kind has no
+// hook) or into side M / N of a least-squares solver (refused on any other); then mk_solver::attach
+int mk_set_precon(mk_solver *s, int side, const MkPrecon &next, const char *who, const char *noun = nullptr);
 
 mk_solver *mk_make_cg();
 mk_solver *mk_make_bicgstab();
@@ -177,12 +207,6 @@ mk_solver *mk_make_tfqmr();
 mk_solver *mk_make_minres();
 mk_solver *mk_make_symmlq();
 mk_solver *mk_make_lls(int kind);
-// M (side 0, nrows(A) entries) or N (side 1, ncols(A) entries) of a least-squares solver: `next` replaces what the side
-// held (MK_PRECON_NONE removes it; MK_PRECON_DIAG comes with the borrowed diagonal `diag`); the other side is untouched
-int mk_lls_set_side(mk_solver *s, int side, const MkPrecon &next, const double *diag, const char *who, const char *noun);
-int mk_lls_side_kind(const mk_solver *s, int side);          // the MkPreconKind that side holds
-// ... a device object (F null: none) on behalf of the entry points that live with the objects' types
-int mk_lls_set_precon_object(mk_solver *s, int side, const MkDeviceOp *F, const char *who, const char *noun);
 
 #ifdef __HIPCC__
 // ------------------------------------------------------------------ small shared kernels
@@ -315,8 +339,10 @@ static inline int mk_launch_spmv_on(mk_solver *s, const mk_csr *M, const double 
 // applies nothing more -- unless `force` (set-up).  `gate` is MkNoGate for every site but N of the least-squares loops,
 // whose product runs under the A' product's own gate (mk_lls.hip, GateV).
 template <class Gate>
-static inline int mk_apply_csr_slot(mk_solver *s, const mk_csr *op, int64_t len, const double *in_dev, double *out_dev,
-                                    bool force, const Gate &gate) {
+static inline int mk_apply_csr_slot(mk_solver *s, const MkPrecon &slot, const double *in_dev, double *out_dev, bool force,
+                                    const Gate &gate) {
+    const mk_csr *op = slot.op;
+    const int64_t len = slot.len;
     double *dst = (in_dev == out_dev) ? s->d_ptmp : out_dev;
     const int grid = mk_grid_spmv_for(op);
     if (force) {

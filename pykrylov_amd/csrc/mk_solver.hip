@@ -7,6 +7,8 @@ int mk_solver::init_common(const mk_csr *A_, const mk_params *p) {
     prm = *p;
     n = A->ex.mode >= 0 ? A->ex.n_local : A->nrows;
     const bool rectangular_ok = prm.kind >= MK_LSQR;
+    slot[0].len = n;
+    slot[1].len = rectangular_ok ? A->ncols : 0;
     if (rectangular_ok && A->ex.mode >= 0)
         return mk_fail(MK_ERR_UNSUPPORTED, "the least-squares solvers partition by row blocks with a replicated column "
                        "space (mk_csr_set_row_block), not with a halo / all-gather exchange plan");
@@ -35,8 +37,8 @@ int mk_solver::init_common(const mk_csr *A_, const mk_params *p) {
     return MK_OK;
 }
 
-int mk_solver::apply_slot(const MkPrecon &slot, int64_t len, const double *in_dev, double *out_dev, bool force,
-                          const double *need_pos) {
+int mk_solver::apply_slot(const MkPrecon &slot, const double *in_dev, double *out_dev, bool force, const double *need_pos) {
+    const int64_t len = slot.len;
     switch (slot.kind) {
         case MK_PRECON_OBJECT: {
             // out = P in by the object's own launches (the factor's sweeps, the chain of the two-loop recursion); each obeys
@@ -46,7 +48,7 @@ int mk_solver::apply_slot(const MkPrecon &slot, int64_t len, const double *in_de
             return rc != MK_OK ? rc : mk_ctx().pending_rc;
         }
         case MK_PRECON_CSR:                                  // out = op * in on the device
-            return mk_apply_csr_slot(this, slot.op, len, in_dev, out_dev, force, MkNoGate());
+            return mk_apply_csr_slot(this, slot, in_dev, out_dev, force, MkNoGate());
         case MK_PRECON_HOST: {
             int h = 0;
             double pos = 1.0;
@@ -76,21 +78,23 @@ void MkPrecon::hold() const {
 void MkPrecon::release() {
     if (kind == MK_PRECON_CSR) mk_release_operand(op);
     if (kind == MK_PRECON_OBJECT) obj->release();
-    *this = MkPrecon{};
-}
-
-void mk_solver::clear_precon() {
-    precon.release();
-    d_prec = nullptr;
+    kind = MK_PRECON_NONE;
+    fn = nullptr;
+    user = nullptr;
+    op = nullptr;
+    obj = nullptr;
+    d = nullptr;
 }
 
 mk_solver::~mk_solver() {
-    if (mk_ctx().ready) hipStreamSynchronize(mk_ctx().stream);
-    clear_precon();
+    if (mk_ctx().ready) hipStreamSynchronize(mk_ctx().stream);   // (an object released below may free its memory)
+    for (MkPrecon &p : slot) {
+        p.release();
+        hipFree(p.ones);
+    }
     if (At) mk_release_operand(At);
     if (A && counted_user) mk_csr_count_users(A, -1);
     if (A) mk_release_operand(A);
-    hipFree(d_ones);
     hipFree(d_ptmp);
     hipFree(d_nohalt);
     if (h_pin) hipHostFree(h_pin);
@@ -333,84 +337,81 @@ extern "C" int mk_csr_set_row_block(mk_csr *A, int on) {
     return MK_OK;
 }
 
-// Every setter below REPLACES whatever preconditioner was attached; a NULL argument leaves the solver with none.
-extern "C" int mk_solver_set_precon_diag(mk_solver *s, const double *diag) {
-    MK_ARG(s);
-    MK_ARG(MK_ALIGNED16(diag));
-    if (diag && !s->takes_precon())
-        return mk_fail(MK_ERR_UNSUPPORTED, "this solver kind has no device preconditioner hook");
-    s->clear_precon();
-    if (diag) s->precon.kind = MK_PRECON_DIAG;
-    s->d_prec = diag;
-    return MK_OK;
-}
+static bool mk_is_lls(const mk_solver *s) { return s->prm.kind >= MK_LSQR && s->prm.kind <= MK_CRAIGMR; }
 
 __global__ __launch_bounds__(MK_BLOCK) void mk_fill_kernel(double *v, int64_t n, double a) {
     for (int64_t i = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MK_BLOCK) v[i] = a;
 }
 
-int mk_solver::attach_precon(const MkPrecon &next, const char *who, const char *noun, const char *plural) {
-    if (!takes_precon()) return mk_fail(MK_ERR_UNSUPPORTED, "this solver kind has no preconditioner hook");
-    // what the kind asks of the solver's operator (only a device matrix may be rank local) and of its own size
+int mk_solver::attach(MkPrecon &into, const MkPrecon &next, const char *who, const char *name, const char *noun) {
+    // what the kind asks of the solver's operator (only a diagonal or a device matrix may be rank local) and of its own size
     if (next.kind == MK_PRECON_HOST && A->ex.mode >= 0)
-        return mk_fail(MK_ERR_UNSUPPORTED, "host preconditioner callbacks are single-GPU (the vector would have to be gathered)");
+        return mk_fail(MK_ERR_UNSUPPORTED, "%s: host preconditioner callbacks are single-GPU (the vector would have to be "
+                       "gathered)", who);
     if (next.kind == MK_PRECON_OBJECT && A->ex.mode >= 0)
-        return mk_fail(MK_ERR_UNSUPPORTED, "%s: %s are single-GPU (the solver's operator carries an exchange plan)", who, plural);
-    if (next.kind == MK_PRECON_OBJECT && next.obj->n != n)
-        return mk_fail(MK_ERR_ARG, "%s: the %s has %lld rows, the solver %lld", who, noun, (long long)next.obj->n, (long long)n);
-    if (next.kind == MK_PRECON_CSR && (next.op->nrows != n || next.op->ncols != n || next.op->ex.mode >= 0))
-        return mk_fail(MK_ERR_ARG, "%s: the preconditioner must be a square device operator of the solver's (local) size %lld "
-                       "without an exchange plan, got %lld x %lld", who, (long long)n, (long long)next.op->nrows,
+        return mk_fail(MK_ERR_UNSUPPORTED, "%s: a device %s is single-GPU (the solver's operator carries an exchange plan)",
+                       who, noun);
+    if (next.kind == MK_PRECON_OBJECT && next.obj->n != into.len)
+        return mk_fail(MK_ERR_ARG, "%s: the %s has %lld rows, %s takes vectors of %lld entries", who, noun,
+                       (long long)next.obj->n, name, (long long)into.len);
+    if (next.kind == MK_PRECON_CSR && (next.op->nrows != into.len || next.op->ncols != into.len || next.op->ex.mode >= 0))
+        return mk_fail(MK_ERR_ARG, "%s: %s must be a square device operator of the (local) size %lld without an exchange "
+                       "plan, got %lld x %lld", who, name, (long long)into.len, (long long)next.op->nrows,
                        (long long)next.op->ncols);
-    const size_t len = (size_t)(n > 0 ? n : 1);
-    if (!d_ones) {
-        MK_HIP(hipMalloc((void **)&d_ones, sizeof(double) * len + 16));
-        hipLaunchKernelGGL(mk_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, stream, d_ones, (int64_t)len, 1.0);
+    const size_t len = (size_t)(into.len > 0 ? into.len : 1);
+    if (next.general() && !into.ones) {                      // (kept until the solver dies)
+        MK_HIP(hipMalloc((void **)&into.ones, sizeof(double) * len + 16));
+        hipLaunchKernelGGL(mk_fill_kernel, dim3(512), dim3(MK_BLOCK), 0, stream, into.ones, (int64_t)len, 1.0);
         MK_HIP(hipGetLastError());
     }
-    if (next.kind == MK_PRECON_HOST && !h_pin) {
-        MK_HIP(hipHostMalloc((void **)&h_pin, sizeof(double) * len, hipHostMallocDefault));
-        MK_HIP(hipHostMalloc((void **)&h_pout, sizeof(double) * len, hipHostMallocDefault));
+    if (next.kind == MK_PRECON_HOST && !h_pin) {             // (one pair of pinned buffers serves both slots)
+        const int64_t longest = slot[0].len > slot[1].len ? slot[0].len : slot[1].len;
+        const size_t cap = (size_t)(longest > 0 ? longest : 1);
+        MK_HIP(hipHostMalloc((void **)&h_pin, sizeof(double) * cap, hipHostMallocDefault));
+        MK_HIP(hipHostMalloc((void **)&h_pout, sizeof(double) * cap, hipHostMallocDefault));
     }
-    if (next.kind == MK_PRECON_CSR && !d_ptmp) MK_HIP(hipMalloc((void **)&d_ptmp, sizeof(double) * len + 16));
+    // only the square solvers precondition a vector in place; M and N are applied out of place (mk_lls.hip)
+    if (next.kind == MK_PRECON_CSR && !mk_is_lls(this) && !d_ptmp) MK_HIP(hipMalloc((void **)&d_ptmp, sizeof(double) * len + 16));
     // take the new reference first, then drop the old one: re-setting the attached object must not free it
     next.hold();
-    clear_precon();
-    precon = next;
-    d_prec = d_ones;
+    into.release();
+    into.kind = next.kind;
+    into.fn = next.fn;
+    into.user = next.user;
+    into.op = next.op;
+    into.obj = next.obj;
+    into.d = next.general() ? into.ones : next.d;
     return MK_OK;
 }
 
-extern "C" int mk_solver_set_precon_callback(mk_solver *s, mk_precon_fn fn, void *user) {
+int mk_set_precon(mk_solver *s, int side, const MkPrecon &next, const char *who, const char *noun) {
     MK_ARG(s);
-    if (!fn) return s->clear_precon(), MK_OK;
-    MkPrecon p;
-    p.kind = MK_PRECON_HOST;
-    p.fn = fn;
-    p.user = user;
-    return s->attach_precon(p, "mk_solver_set_precon_callback");
+    if (side < 0) {
+        if (!s->takes_precon())                              // (its slot is empty and stays so: nothing to remove)
+            return next.kind == MK_PRECON_NONE ? (int)MK_OK
+                                               : mk_fail(MK_ERR_UNSUPPORTED, "%s: this solver kind has no preconditioner hook", who);
+        return s->attach(s->slot[0], next, who, "the preconditioner", noun);
+    }
+    MK_ARG(side == MK_LLS_SIDE_M || side == MK_LLS_SIDE_N);
+    if (!mk_is_lls(s)) return mk_fail(MK_ERR_UNSUPPORTED, "%s: not a least-squares solver", who);
+    return s->attach(s->slot[side], next, who, side == MK_LLS_SIDE_N ? "N" : "M", noun);
+}
+
+// Every setter REPLACES whatever its slot held; a NULL argument leaves the slot empty.  (The setters of the device objects,
+// mk_solver_set_precon_ilu / _lbfgs / _cheb and mk_solver_set_lls_precon_ilu / _bfgs / _cheb, live with their types in
+// mk_ilu.hip / mk_lbfgs.hip / mk_cheb.hip.)
+extern "C" int mk_solver_set_precon_diag(mk_solver *s, const double *diag) {
+    MK_ARG(MK_ALIGNED16(diag));
+    return mk_set_precon(s, -1, MkPrecon::diagonal(diag), "mk_solver_set_precon_diag");
+}
+
+extern "C" int mk_solver_set_precon_callback(mk_solver *s, mk_precon_fn fn, void *user) {
+    return mk_set_precon(s, -1, MkPrecon::callback(fn, user), "mk_solver_set_precon_callback");
 }
 
 extern "C" int mk_solver_set_precon_csr(mk_solver *s, const mk_csr *M) {
-    MK_ARG(s);
-    if (!M) return s->clear_precon(), MK_OK;
-    MkPrecon p;
-    p.kind = MK_PRECON_CSR;
-    p.op = M;
-    return s->attach_precon(p, "mk_solver_set_precon_csr");
+    return mk_set_precon(s, -1, MkPrecon::matrix(M), "mk_solver_set_precon_csr");
 }
-
-// (the entry points of the objects, mk_solver_set_precon_ilu / _bfgs, live with their types in mk_ilu.hip / mk_lbfgs.hip)
-int mk_set_precon_object(mk_solver *s, const MkDeviceOp *F, const char *who, const char *noun, const char *plural) {
-    MK_ARG(s);
-    if (!F) return s->clear_precon(), MK_OK;
-    MkPrecon p;
-    p.kind = MK_PRECON_OBJECT;
-    p.obj = F;
-    return s->attach_precon(p, who, noun, plural);
-}
-
-static bool mk_is_lls(const mk_solver *s) { return s->prm.kind >= MK_LSQR && s->prm.kind <= MK_CRAIGMR; }
 
 // The two-sided setters: a side that is given something takes it in place of what it held; a side that is given NULL
 // loses what THIS setter attaches (a diagonal here, a callback below) and keeps anything else.
@@ -420,10 +421,8 @@ extern "C" int mk_solver_set_lls_precon(mk_solver *s, const double *diag_m, cons
     if (!mk_is_lls(s)) return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_set_lls_precon: not a least-squares solver");
     const double *diag[2] = {diag_m, diag_n};
     for (int side = 0; side < 2; ++side) {
-        MkPrecon p;
-        if (diag[side]) p.kind = MK_PRECON_DIAG;
-        else if (mk_lls_side_kind(s, side) != MK_PRECON_DIAG) continue;
-        const int rc = mk_lls_set_side(s, side, p, diag[side], "mk_solver_set_lls_precon", nullptr);
+        if (!diag[side] && s->slot[side].kind != MK_PRECON_DIAG) continue;
+        const int rc = mk_set_precon(s, side, MkPrecon::diagonal(diag[side]), "mk_solver_set_lls_precon");
         if (rc != MK_OK) return rc;
     }
     return MK_OK;
@@ -436,43 +435,15 @@ extern "C" int mk_solver_set_lls_precon_callback(mk_solver *s, mk_precon_fn fn_m
     const mk_precon_fn fn[2] = {fn_m, fn_n};
     void *const user[2] = {user_m, user_n};
     for (int side = 0; side < 2; ++side) {
-        MkPrecon p;
-        if (fn[side]) {
-            p.kind = MK_PRECON_HOST;
-            p.fn = fn[side];
-            p.user = user[side];
-        } else if (mk_lls_side_kind(s, side) != MK_PRECON_HOST) {
-            continue;
-        }
-        const int rc = mk_lls_set_side(s, side, p, nullptr, "mk_solver_set_lls_precon_callback", nullptr);
+        if (!fn[side] && s->slot[side].kind != MK_PRECON_HOST) continue;
+        const int rc = mk_set_precon(s, side, MkPrecon::callback(fn[side], user[side]), "mk_solver_set_lls_precon_callback");
         if (rc != MK_OK) return rc;
     }
     return MK_OK;
 }
 
 extern "C" int mk_solver_set_lls_precon_csr(mk_solver *s, int side, const mk_csr *P) {
-    MK_ARG(s);
-    MK_ARG(side == MK_LLS_SIDE_M || side == MK_LLS_SIDE_N);
-    if (!mk_is_lls(s)) return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_set_lls_precon_csr: not a least-squares solver");
-    MkPrecon p;
-    if (P) {
-        p.kind = MK_PRECON_CSR;
-        p.op = P;
-    }
-    return mk_lls_set_side(s, side, p, nullptr, "mk_solver_set_lls_precon_csr", nullptr);
-}
-
-// (the entry points of the objects, mk_solver_set_lls_precon_ilu / _bfgs, live with their types in mk_ilu.hip / mk_lbfgs.hip)
-int mk_lls_set_precon_object(mk_solver *s, int side, const MkDeviceOp *F, const char *who, const char *noun) {
-    MK_ARG(s);
-    MK_ARG(side == MK_LLS_SIDE_M || side == MK_LLS_SIDE_N);
-    if (!mk_is_lls(s)) return mk_fail(MK_ERR_UNSUPPORTED, "%s: not a least-squares solver", who);
-    MkPrecon p;
-    if (F) {
-        p.kind = MK_PRECON_OBJECT;
-        p.obj = F;
-    }
-    return mk_lls_set_side(s, side, p, nullptr, who, noun);
+    return mk_set_precon(s, side, MkPrecon::matrix(P), "mk_solver_set_lls_precon_csr");
 }
 
 extern "C" int mk_solver_destroy(mk_solver *s) {
@@ -540,20 +511,22 @@ extern "C" int mk_solver_unapplied(const mk_solver *s, int64_t *count) {
     return MK_OK;
 }
 
-extern "C" int mk_solver_history(const mk_solver *s, double *hist_host, int64_t cap) {
-    MK_ARG(s && (cap == 0 || hist_host));
-    int64_t cnt = (int64_t)s->hist.size();
+static int mk_copy_history(const std::vector<double> &hist, double *hist_host, int64_t cap) {
+    MK_ARG(cap == 0 || hist_host);
+    int64_t cnt = (int64_t)hist.size();
     if (cnt > cap) cnt = cap;
-    memcpy(hist_host, s->hist.data(), sizeof(double) * (size_t)cnt);
+    memcpy(hist_host, hist.data(), sizeof(double) * (size_t)cnt);
     return MK_OK;
 }
 
+extern "C" int mk_solver_history(const mk_solver *s, double *hist_host, int64_t cap) {
+    MK_ARG(s);
+    return mk_copy_history(s->hist, hist_host, cap);
+}
+
 extern "C" int mk_solver_history2(const mk_solver *s, double *hist_host, int64_t cap) {
-    MK_ARG(s && (cap == 0 || hist_host));
-    int64_t cnt = (int64_t)s->hist2.size();
-    if (cnt > cap) cnt = cap;
-    memcpy(hist_host, s->hist2.data(), sizeof(double) * (size_t)cnt);
-    return MK_OK;
+    MK_ARG(s);
+    return mk_copy_history(s->hist2, hist_host, cap);
 }
 
 extern "C" int mk_solver_vector(const mk_solver *s, int index, const double **v_dev, int64_t *len) {

@@ -545,9 +545,9 @@ struct SymmlqSolver : mk_solver {
         mk_launch_stream(this, MkOpCopy{rhs, d_r[0]}, n);                      // r1 = rhs.copy()   symmlq.py:129
         mk_launch_stream(this, MkOpCopy{rhs, d_r[1]}, n);                      // y = rhs.copy()    symmlq.py:133
         int rc;
-        if (d_prec && !d_y && (rc = alloc_vec(&d_y, nx))) return rc;
-        double *y0 = d_prec ? d_y : d_r[1];
-        if (d_prec) mk_launch_stream(this, MkOpMul{d_prec, d_r[0], d_y}, n);   // y = precon * r1   symmlq.py:131-132
+        if (d_prec() && !d_y && (rc = alloc_vec(&d_y, nx))) return rc;
+        double *y0 = d_prec() ? d_y : d_r[1];
+        if (d_prec()) mk_launch_stream(this, MkOpMul{d_prec(), d_r[0], d_y}, n);   // y = precon * r1   symmlq.py:131-132
         if (general_precon() && (rc = apply_precon(d_r[0], d_y)) != MK_OK) return rc;
         mk_launch_stream(this, MkOpDot<SLOT_A>{d_r[0], y0}, n);                // beta1             symmlq.py:134
         if ((rc = allreduce(SLOT_A, 1)) != MK_OK) return rc;
@@ -557,7 +557,7 @@ struct SymmlqSolver : mk_solver {
         if ((rc = allreduce(SLOT_B, 1)) != MK_OK) return rc;
         mk_launch_stream(this, OpS3{d_part, np_spmv, d_scal, d_r[0], d_v, d_t, 0.0}, n);
         if ((rc = allreduce(SLOT_C, 2)) != MK_OK) return rc;
-        mk_launch_stream(this, OpS4{d_part, np_stream, d_scal, d_t, d_v, d_r[1], d_prec, d_y, 0.0}, n);
+        mk_launch_stream(this, OpS4{d_part, np_stream, d_scal, d_t, d_v, d_r[1], d_prec(), d_y, 0.0}, n);
         if (general_precon()) {                             // y = precon * r2 ; <r2, y> re-formed   symmlq.py:188-190
             if ((rc = apply_precon(d_r[1], d_y)) != MK_OK) return rc;
             mk_launch_stream(this, MkOpDot<SLOT_A>{d_r[1], d_y}, n);
@@ -572,7 +572,7 @@ struct SymmlqSolver : mk_solver {
         if (which != 0) return mk_fail(MK_ERR_ARG, "SYMMLQ has one product per pass");
         const double *blk = d_scal + S_BLK + (int)(it & 1) * BLK;
         double *r1 = d_r[it & 1], *r2 = d_r[(it + 1) & 1];
-        double *y = d_prec ? d_y : r2;
+        double *y = d_prec() ? d_y : r2;
         mk_launch_spmv(this, y, EpiK1{blk, y, r1, d_v, d_t, prm.shift, prm.has_shift, 0.0, 0.0, mk_store_nt(A)}, false);
         return MK_OK;
     }
@@ -581,13 +581,13 @@ struct SymmlqSolver : mk_solver {
         const int par = (int)(it & 1);
         const double *blk = d_scal + S_BLK + par * BLK;
         double *r1 = d_r[it & 1], *r2 = d_r[(it + 1) & 1];
-        double *y = d_prec ? d_y : r2;                                         // symmlq.py:308-309
+        double *y = d_prec() ? d_y : r2;                                         // symmlq.py:308-309
         int rc = exchange(y);
         if (rc != MK_OK) return rc;
         mk_launch_spmv(this, y, EpiK1{blk, y, r1, d_v, d_t, prm.shift, prm.has_shift, 0.0, 0.0, mk_store_nt(A)}, true,
                        CountGate{d_status, 1 + it});
         if ((rc = allreduce(SLOT_A, 1)) != MK_OK) return rc;
-        mk_launch_stream(this, OpK2{d_part, np_spmv, d_scal, blk, r2, d_t, r1, d_prec, d_y, 0.0}, n);
+        mk_launch_stream(this, OpK2{d_part, np_spmv, d_scal, blk, r2, d_t, r1, d_prec(), d_y, 0.0}, n);
         if (general_precon()) {                             // y = precon * r2 ; <r2, y> re-formed   symmlq.py:308-310
             if ((rc = apply_precon(r1, d_y)) != MK_OK) return rc;          // (OpK2 wrote the new r2 into r1's storage)
             mk_launch_stream(this, MkOpDot<SLOT_B>{r1, d_y}, n);
@@ -621,7 +621,7 @@ struct SymmlqSolver : mk_solver {
                 bdir = d_t;                                  // (with the unit diagonal the kernel multiplies it by 1.0)
             }
             hipLaunchKernelGGL(mk_stream_kernel<OpFinX>, dim3(mk_grid_stream(n)), dim3(MK_BLOCK), 0, stream,
-                               OpFinX{d_w, bdir, d_x, d_prec, zbar, bstep, cg_point}, n, nh, d_part);
+                               OpFinX{d_w, bdir, d_x, d_prec(), zbar, bstep, cg_point}, n, nh, d_part);
             if ((rc = allreduce(SLOT_A, 1)) != MK_OK) return rc;
             if ((rc = exchange(d_x)) != MK_OK) return rc;
             if ((rc = mk_exchange_wait(A, stream)) != MK_OK) return rc;      // one launch over all tiles below

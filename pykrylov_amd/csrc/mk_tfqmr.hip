@@ -303,7 +303,7 @@ struct TfqmrSolver : mk_solver {
     double *d_x = nullptr, *d_r0 = nullptr, *d_y = nullptr, *d_w = nullptr, *d_d = nullptr, *d_u = nullptr,
            *d_v = nullptr, *d_z = nullptr;
     bool takes_precon() const override { return true; }
-    double *zsrc() const { return d_prec ? d_z : d_y; }                        // what the products and `d += z` read
+    double *zsrc() const { return d_prec() ? d_z : d_y; }                        // what the products and `d += z` read
 
     int setup(const double *rhs, const double *guess) override {
         if (!d_x) {
@@ -313,7 +313,7 @@ struct TfqmrSolver : mk_solver {
                 (rc = alloc_vec(&d_v, n)))
                 return rc;
         }
-        if (d_prec && !d_z) {
+        if (d_prec() && !d_z) {
             int rc = alloc_vec(&d_z, nx);
             if (rc) return rc;
         }
@@ -335,7 +335,7 @@ struct TfqmrSolver : mk_solver {
         mk_launch_stream(this, MkOpCopy{d_r0, d_y}, n);                        // y = r0.copy()    tfqmr.py:70
         mk_launch_stream(this, MkOpCopy{d_r0, d_w}, n);                        // w = r0.copy()    tfqmr.py:71
         MK_HIP(hipMemsetAsync(d_d, 0, sizeof(double) * (size_t)n, stream));    // d = 0            tfqmr.py:72
-        if (d_prec) mk_launch_stream(this, MkOpMul{d_prec, d_r0, d_z}, n);     // z = precon * y   tfqmr.py:77-78
+        if (d_prec()) mk_launch_stream(this, MkOpMul{d_prec(), d_r0, d_z}, n);     // z = precon * y   tfqmr.py:77-78
         if (general_precon() && apply_precon(d_y, d_z) != MK_OK) return MK_ERR_STATE;
         if ((rc = exchange(zsrc())) != MK_OK) return rc;
         // u = A z ; v = u.copy() ; first sigma                               tfqmr.py:82-83
@@ -360,13 +360,13 @@ struct TfqmrSolver : mk_solver {
         mk_launch_stream(this, OpP2{d_part, np_spmv, d_scal, par, d_u, zs, d_w, d_d, 0.0, 0.0}, n);
         if ((rc = allreduce(SLOT_WW, 1)) != MK_OK) return rc;
         mk_launch_stream(this, OpP3{d_part, np_stream, d_scal, d_status, prm.matvec_max, nmv, k, d_d, d_v, d_x, d_y,
-                                    d_prec, d_z, 0.0, 0.0, false}, n);
+                                    d_prec(), d_z, 0.0, 0.0, false}, n);
         if (general_precon() && (rc = apply_precon(d_y, d_z)) != MK_OK) return rc;     // z = precon * y       tfqmr.py:109-110
         if ((rc = exchange(zs)) != MK_OK) return rc;
         mk_launch_spmv(this, zs, EpiP4{d_scal, zs, d_r0, d_u, d_w, d_d, 0.0, 0.0}, true, CountGate{d_status, nmv});
         if ((rc = allreduce(SLOT_WW, 2)) != MK_OK) return rc;
         mk_launch_stream(this, OpP5{d_part, np_spmv, d_scal, d_status, par, prm.matvec_max, nmv + 1, k, d_d, d_w, d_u,
-                                    d_x, d_y, d_v, d_prec, d_z, 0.0, 0.0, false}, n);
+                                    d_x, d_y, d_v, d_prec(), d_z, 0.0, 0.0, false}, n);
         if (general_precon() && (rc = apply_precon(d_y, d_z)) != MK_OK) return rc;     // z = precon * y       tfqmr.py:142-143
         if ((rc = exchange(zs)) != MK_OK) return rc;
         mk_launch_spmv(this, zs, EpiP6<false>{d_r0, d_u, d_v}, true, CountGate{d_status, nmv + 1});

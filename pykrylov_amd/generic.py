@@ -82,70 +82,11 @@ class KrylovMethod(object):
         return sh
 
     def _device_precon(self, precon):
-        """How the device loop applies ``precon * r`` (generic.py:76; cg.py:91-92, bicgstab.py:96-99, ...):
-
-        * an operator that exposes its diagonal (``DiagonalOperator``, linop.py:473-516 -- the docs' Jacobi
-          `DiagonalPrec`, examples/bmark.py:14-23) is returned as an fp64 array and applied INSIDE the kernels;
-        * anything else with ``precon * vector`` is returned wrapped in :class:`HostPrecon`: the loop stays on the
-          device and calls it back on the host at each preconditioner site."""
-        if precon is None:
-            return None
-        diag = getattr(precon, 'diag', None)
-        if diag is not None and not callable(diag):
-            n = self.op.shape[0]
-            return as_f64_vector(diag, getattr(self.op, 'local_size', None) or n, 'precon.diag')
-        # * an incomplete factorization (`tools.ilu0` / `tools.ic0`) is applied ON the device by its triangular sweeps
-        from .tools import IluPreconditioner
-        if isinstance(precon, IluPreconditioner):
-            if getattr(self.op, 'local_size', None) is not None:
-                raise NotImplementedError('%s: incomplete factorizations are single-GPU; the operator is row-partitioned'
-                                          % self.__class__.__name__)
-            if precon.shape != (self.op.shape[0], self.op.shape[0]):
-                raise ValueError('%s: precon has shape %s, expected %s'
-                                 % (self.__class__.__name__, precon.shape, (self.op.shape[0], self.op.shape[0])))
-            return precon
-        # * an inverse L-BFGS operator (`lbfgs.InverseLBFGSOperator`) is applied ON the device by its two-loop recursion;
-        #   the forward classes are not preconditioners and stay on the host-callback route below
-        from .lbfgs import InverseLBFGSOperator
-        if isinstance(precon, InverseLBFGSOperator) and precon._is_inverse:
-            if getattr(self.op, 'local_size', None) is not None:
-                raise NotImplementedError('%s: L-BFGS operators are single-GPU; the operator is row-partitioned'
-                                          % self.__class__.__name__)
-            if precon.shape != (self.op.shape[0], self.op.shape[0]):
-                raise ValueError('%s: precon has shape %s, expected %s'
-                                 % (self.__class__.__name__, precon.shape, (self.op.shape[0], self.op.shape[0])))
-            return precon
-        # * a Chebyshev polynomial preconditioner (`tools.chebyshev`) is applied ON the device: one product of its matrix per
-        #   step, the step's vector updates fused into the product's row epilogue
-        from .tools import ChebyshevPreconditioner
-        if isinstance(precon, ChebyshevPreconditioner):
-            if getattr(self.op, 'local_size', None) is not None:
-                raise NotImplementedError('%s: Chebyshev preconditioners are single-GPU; the operator is row-partitioned'
-                                          % self.__class__.__name__)
-            if precon.shape != (self.op.shape[0], self.op.shape[0]):
-                raise ValueError('%s: precon has shape %s, expected %s'
-                                 % (self.__class__.__name__, precon.shape, (self.op.shape[0], self.op.shape[0])))
-            return precon
-        # * a device matrix (CsrOperator -- e.g. the inverted diagonal blocks of `tools.block_jacobi`) or a block
-        #   operator of device matrices is applied ON the device, as a product at the same sites
-        from .linop import CsrOperator
-        dev = precon if isinstance(precon, CsrOperator) else None
-        if dev is None and hasattr(precon, '_device_view'):
-            dev = precon._device_view()
-        if dev is not None and getattr(dev, 'local_size', None) is None:
-            nloc = getattr(self.op, 'local_size', None) or self.op.shape[0]
-            if dev.shape != (nloc, nloc):
-                raise ValueError('%s: precon has shape %s, expected %s' % (self.__class__.__name__, dev.shape, (nloc, nloc)))
-            return DevicePrecon(precon, dev)
-        if not hasattr(precon, '__mul__') and not callable(precon):
-            raise TypeError('%s: precon must support `precon * vector`; got %r'
-                            % (self.__class__.__name__, type(precon).__name__))
-        if getattr(self.op, 'local_size', None) is not None:
-            raise NotImplementedError('%s: on a row-partitioned operator a preconditioner must be rank local and live on '
-                                      'the device: a DiagonalOperator slice, or a device matrix / composite of the local '
-                                      'size (e.g. pykrylov_amd.tools.block_jacobi(op, bs) of the partitioned operator); '
-                                      'host callables are not called back across ranks' % self.__class__.__name__)
-        return HostPrecon(precon)
+        """How the device loop applies ``precon * r`` (generic.py:76; cg.py:91-92, bicgstab.py:96-99, ...): the payload of
+        :func:`resolve_precon` -- ``None``, an fp64 array (a diagonal), the device object itself, a
+        :class:`DevicePrecon` or a :class:`HostPrecon`."""
+        part = getattr(self.op, 'local_size', None)
+        return resolve_precon(precon, part or self.op.shape[0], 'precon', self.__class__.__name__, part is not None)[1]
 
     def _logging(self):
         return self.logger is not null_log and self.logger.isEnabledFor(logging.INFO)
@@ -163,12 +104,104 @@ class DevicePrecon(object):
 
 
 class HostPrecon(object):
-    """A general preconditioner for the device loop: ``precon * r`` evaluated on the host through a callback."""
+    """A general preconditioner for the device loop, evaluated on the host through a callback.  A square solver's
+    ``precon`` is applied as the reference's loops do, ``precon * r`` (``precon(r)`` if it has no ``__mul__``); M and N of
+    the least-squares solvers (`call_first`) as theirs do, ``P(v)`` (``P * v`` if it is not callable: lsqr.py:190,202)."""
 
-    def __init__(self, precon):
+    def __init__(self, precon, call_first=False):
         self.precon = precon
+        self.call_first = call_first
         self.error = None
         self.calls = 0
+
+    def apply(self, r):
+        p = self.precon
+        if self.call_first:
+            return p(r) if callable(p) else p * r
+        return p * r if hasattr(p, '__mul__') else p(r)
+
+    def thunk(self, n):
+        """The C callback on vectors of `n` entries.  What the preconditioner raises must not propagate through the C
+        frames: the first exception is kept in `error` for the caller (DeviceRun._check) to re-raise."""
+        def as_vector(ptr):
+            return np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_double)), shape=(n,))
+
+        def call(user, rp, yp):
+            try:
+                y = np.asarray(self.apply(as_vector(rp).copy()))
+                if y.shape != (n,):
+                    raise ValueError('the preconditioner returned shape %s, expected (%d,)' % (y.shape, n))
+                as_vector(yp)[:] = y
+                self.calls += 1
+                return 0
+            except BaseException as exc:                    # noqa: B902
+                if self.error is None:                      # (keep the root cause, not a follow-up failure)
+                    self.error = exc
+                return 1
+        return _lib.PRECON_FN(call)
+
+
+def _device_object_route(precon):
+    """The route word of a preconditioner that is a device object of the library, and its plural for messages."""
+    from .tools import ChebyshevPreconditioner, IluPreconditioner
+    from .lbfgs import InverseLBFGSOperator
+    if isinstance(precon, IluPreconditioner):                # `tools.ilu0` / `tools.ic0`: triangular sweeps
+        return 'ilu', 'incomplete factorizations'
+    # (the forward L-BFGS classes are not preconditioners and stay on the host-callback route)
+    if isinstance(precon, InverseLBFGSOperator) and precon._is_inverse:    # the two-loop recursion
+        return 'lbfgs', 'L-BFGS operators'
+    if isinstance(precon, ChebyshevPreconditioner):          # `tools.chebyshev`: one product of its matrix per step
+        return 'cheb', 'Chebyshev preconditioners'
+    return None, None
+
+
+def resolve_precon(precon, size, name, owner, partitioned=False):
+    """How a device loop applies a preconditioner to vectors of `size` entries: ``precon`` of a square solver
+    (``precon * r``: cg.py:91-92, bicgstab.py:96-99, ...) and M / N of a least-squares solver (`u = M(Mu)`, `v = N(Nv)`:
+    lsqr.py:190,202,254,266).  `name` ('precon', 'M', 'N') and `owner` (the solver's class name) go into the messages;
+    `partitioned`: the solver's operator is row-partitioned.  Returns ``(route, payload)``, the route in the words of
+    ``DeviceRun.precon_kind``:
+
+    * ``'none'``, ``None``;
+    * ``'diag'``: an operator that exposes its diagonal (``DiagonalOperator``, linop.py:473-516 -- the docs' Jacobi
+      `DiagonalPrec`, examples/bmark.py:14-23) -- the fp64 array, applied INSIDE the kernels;
+    * ``'ilu'`` / ``'lbfgs'`` / ``'cheb'``: a device object of the library -- itself, applied ON the device by its own
+      launches;
+    * ``'device'``: a CsrOperator, or an operator with a device view (`tools.block_jacobi`, block operators of device
+      matrices), square and of that size -- a :class:`DevicePrecon`, a product on the device;
+    * ``'host'``: anything else that can be applied to a vector -- a :class:`HostPrecon`: the loop stays on the device and
+      calls it back on the host at each preconditioner site."""
+    if precon is None:
+        return 'none', None
+
+    def check_shape(shape):
+        if tuple(shape) != (size, size):
+            raise ValueError('%s: %s has shape %s, expected %s' % (owner, name, tuple(shape), (size, size)))
+    diag = getattr(precon, 'diag', None)
+    if diag is not None and not callable(diag):
+        return 'diag', as_f64_vector(diag, size, name + '.diag')
+    route, plural = _device_object_route(precon)
+    if route is not None:
+        if partitioned:
+            raise NotImplementedError('%s: %s are single-GPU; the operator is row-partitioned' % (owner, plural))
+        check_shape(precon.shape)
+        return route, precon
+    from .linop import CsrOperator
+    dev = precon if isinstance(precon, CsrOperator) else None
+    if dev is None and hasattr(precon, '_device_view'):
+        dev = precon._device_view()
+    if dev is not None and getattr(dev, 'local_size', None) is None:
+        check_shape(dev.shape)
+        return 'device', DevicePrecon(precon, dev)
+    if not hasattr(precon, '__mul__') and not callable(precon):
+        raise TypeError('%s: %s must support `%s * vector` or be callable; got %r'
+                        % (owner, name, name, type(precon).__name__))
+    if partitioned:
+        raise NotImplementedError('%s: on a row-partitioned operator a preconditioner must be rank local and live on '
+                                  'the device: a DiagonalOperator slice, or a device matrix / composite of the local '
+                                  'size (e.g. pykrylov_amd.tools.block_jacobi(op, bs) of the partitioned operator); '
+                                  'host callables are not called back across ranks' % owner)
+    return 'host', HostPrecon(precon, call_first=name != 'precon')
 
 
 def as_f64_vector(v, n, what):
@@ -186,10 +219,11 @@ class DeviceRun(object):
     def __init__(self, op, kind, rhs, guess=None, precon_diag=None, **params):
         self.lib = _lib.init()
         self.op = op
-        self.precon_kind, self.precon = 'none', None
+        self.precon_kind, self.precon, self.sides = 'none', None, None
         # `transpose`: the device operator A.T the least-squares kinds need (mk_solver_set_transpose); their rhs has
-        # nrows(A) entries.  `placement_draws`: see _draws().
+        # nrows(A) entries.  `sides`: their M and N, a pair of `resolve_precon` payloads.  `placement_draws`: see _draws().
         transpose = params.pop('transpose', None)
+        sides = params.pop('sides', None)
         draws = params.pop('placement_draws', None)
         if draws is not None:
             self.placement_draws = int(draws)
@@ -216,9 +250,9 @@ class DeviceRun(object):
         _lib.check(self.lib.mk_solver_create(op.handle, ctypes.byref(p), ctypes.byref(self.handle)))
         self.transpose = transpose
         try:                                                 # (no handle may outlive a failed constructor)
-            self.precon_kind, self.precon, self._attach = self._resolve_precon(precon_diag, n)
-            if isinstance(precon_diag, _lib.DeviceArray):    # (a diagonal already resident in HBM: the caller's)
-                self._borrowed.append(precon_diag)
+            self._borrowed += [p for p in (precon_diag,) + tuple(sides or ()) if isinstance(p, _lib.DeviceArray)]
+            self.precon_kind, self.precon, self._precon_arg = self._resolve_precon(precon_diag, n)
+            self.sides = None if sides is None else [self._resolve_precon(p, k) for p, k in zip(sides, op.shape)]
             self._apply_precon(self.handle)
         except Exception:
             self.lib.mk_solver_destroy(self.handle)
@@ -229,51 +263,34 @@ class DeviceRun(object):
         self.placement = {"count": 1, "chosen": 0, "per_draw_ms_per_pass": [], "probe_seconds": 0.0, "passes_per_draw": 0}
 
     def _resolve_precon(self, precon, n):
-        """The one preconditioner of this run, as `_device_precon` returned it: its kind, the object to keep alive (for a
-        diagonal the DeviceArray, which `close` frees unless it is the caller's) and the call that attaches it to a solver
-        handle (the constructor's, and every placement draw's)."""
-        lib = self.lib
-        from .tools import ChebyshevPreconditioner, IluPreconditioner
-        from .lbfgs import InverseLBFGSOperator
+        """A preconditioner on vectors of `n` entries as `resolve_precon` returned it: its kind, the object this run keeps
+        for it (a diagonal: the DeviceArray, which `close` frees unless it is the caller's) and a call that gives what the
+        C setter of the kind takes."""
         if precon is None:
-            return 'none', None, lambda handle: 0
-        if isinstance(precon, ChebyshevPreconditioner):
-            return 'cheb', precon, lambda handle: lib.mk_solver_set_precon_cheb(handle, precon._live())
-        if isinstance(precon, IluPreconditioner):
-            return 'ilu', precon, lambda handle: lib.mk_solver_set_precon_ilu(handle, precon._live())
-        if isinstance(precon, InverseLBFGSOperator) and precon._is_inverse:
-            return 'lbfgs', precon, lambda handle: lib.mk_solver_set_precon_lbfgs(handle, precon._live())
+            return 'none', None, None
+        if _device_object_route(precon)[0] is not None:
+            return _device_object_route(precon)[0], precon, precon._live
         if isinstance(precon, DevicePrecon):
-            return 'device', precon, lambda handle: lib.mk_solver_set_precon_csr(handle, precon.dev.handle)
+            return 'device', precon, lambda: precon.dev.handle
         if isinstance(precon, HostPrecon):
-            hp = precon
-
-            def call(user, rp, yp):
-                try:
-                    r = np.ctypeslib.as_array(ctypes.cast(rp, ctypes.POINTER(ctypes.c_double)), shape=(n,)).copy()
-                    y = np.asarray(hp.precon * r if hasattr(hp.precon, '__mul__') else hp.precon(r))
-                    if y.shape != (n,):
-                        raise ValueError('precon * r has shape %s, expected (%d,)' % (y.shape, n))
-                    np.ctypeslib.as_array(ctypes.cast(yp, ctypes.POINTER(ctypes.c_double)), shape=(n,))[:] = y
-                    hp.calls += 1
-                    return 0
-                except BaseException as exc:                # noqa: B902  (must not propagate through the C frames)
-                    if hp.error is None:                    # (keep the root cause, not a follow-up failure)
-                        hp.error = exc
-                    return 1
-            cb = _lib.PRECON_FN(call)                       # (the closure below keeps the thunk alive)
-            return 'host', hp, lambda handle: lib.mk_solver_set_precon_callback(handle, cb, None)
-        # a diagonal: a DeviceArray already resident in HBM, or a host array (copied there)
+            cb = precon.thunk(n)                             # (the closure keeps the thunk alive)
+            return 'host', precon, lambda: cb
+        # a diagonal: a DeviceArray already resident in HBM (the caller's), or a host array (copied there)
         d = precon if isinstance(precon, _lib.DeviceArray) else \
             _lib.DeviceArray.from_numpy(as_f64_vector(precon, n, 'precon.diag'))
-        return 'diag', d, lambda handle: lib.mk_solver_set_precon_diag(handle, d.ptr)
+        return 'diag', d, lambda: d.ptr
+
+    def _slots(self):
+        """(kind, kept object) of every preconditioner of this run: the square solver's, then M and N."""
+        return [(self.precon_kind, self.precon)] + [(kind, p) for kind, p, _ in self.sides or ()]
 
     def _check(self, rc):
         if rc != 0 and hasattr(self.op, 'raise_pending'):
             self.op.raise_pending()                           # what a matrix-free operator raised in its callback
-        if rc != 0 and self.precon_kind == 'host' and self.precon.error is not None:
-            err, self.precon.error = self.precon.error, None
-            raise err
+        for kind, hp in self._slots():                        # ... or a host preconditioner in its
+            if rc != 0 and kind == 'host' and hp.error is not None:
+                err, hp.error = hp.error, None
+                raise err
         _lib.check(rc)
 
     # Placement draws (DESIGN.md 3.2) -- OPT-IN since round 4 (MK_PLACEMENT_DRAWS=k > 1, or `placement_draws=k` on the
@@ -313,7 +330,7 @@ class DeviceRun(object):
         min_mb = float(os.environ.get('MK_PLACEMENT_MIN_MB', '256'))      # (tests lower it to draw on small problems)
         if want <= 1 or 8 * self.n <= min_mb * 1024 * 1024:
             return 1
-        if getattr(self.op, 'local_size', None) is not None or self.precon_kind == 'host':
+        if getattr(self.op, 'local_size', None) is not None or 'host' in [kind for kind, _ in self._slots()]:
             return 1
         from .linop import CsrOperator
         if not isinstance(self.op, CsrOperator):             # (matrix-free shells: every pass calls back to the host)
@@ -327,9 +344,29 @@ class DeviceRun(object):
         return min(want, 8)
 
     def _apply_precon(self, handle):
-        if getattr(self, 'transpose', None) is not None:
-            _lib.check(self.lib.mk_solver_set_transpose(handle, self.transpose.handle))
-        _lib.check(self._attach(handle))
+        """Attach the transpose and the preconditioner(s) to a solver handle (the constructor's, and every placement
+        draw's)."""
+        lib = self.lib
+        if self.transpose is not None:
+            _lib.check(lib.mk_solver_set_transpose(handle, self.transpose.handle))
+        if self.precon_kind != 'none':
+            setter = {'host': 'callback', 'device': 'csr'}.get(self.precon_kind, self.precon_kind)
+            user = (None,) if self.precon_kind == 'host' else ()
+            _lib.check(getattr(lib, 'mk_solver_set_precon_' + setter)(handle, self._precon_arg(), *user))
+        if self.sides is None:
+            return
+        # M and N: the callbacks, then the diagonals (a NULL side of these two setters leaves another kind alone), then
+        # the device kinds side by side
+        kinds = [kind for kind, _, _ in self.sides]
+        if 'host' in kinds:
+            fns = [arg() if kind == 'host' else ctypes.cast(None, _lib.PRECON_FN) for kind, _, arg in self.sides]
+            _lib.check(lib.mk_solver_set_lls_precon_callback(handle, fns[0], None, fns[1], None))
+        if 'diag' in kinds:
+            _lib.check(lib.mk_solver_set_lls_precon(handle, *[arg() if kind == 'diag' else None for kind, _, arg in self.sides]))
+        for side, (kind, _, arg) in enumerate(self.sides):
+            if kind not in ('none', 'host', 'diag'):
+                setter = {'device': 'csr', 'lbfgs': 'bfgs'}.get(kind, kind)
+                _lib.check(getattr(lib, 'mk_solver_set_lls_precon_' + setter)(handle, side, arg()))
 
     def _timed_passes(self, handle, warm=4, passes=12):
         g = None if self.d_guess is None else self.d_guess.ptr
@@ -436,6 +473,12 @@ class DeviceRun(object):
         _lib.check(self.lib.mk_solver_history(self.handle, out.ctypes.data, n))
         return out
 
+    def history2(self):
+        """The second history channel (MINRES, least squares: the direct-error estimates)."""
+        out = np.empty(int(self.result.hist_len), dtype=np.float64)
+        _lib.check(self.lib.mk_solver_history2(self.handle, out.ctypes.data, len(out)))
+        return out
+
     def time_product(self, which=0, launches=200):
         """Average duration (us) of the pass's product kernel `which` (0 first, 1 second / A.T), launched back to
         back without its gate and bracketed by one HIP event pair.  Destroys the loop's vectors: call it last."""
@@ -453,8 +496,8 @@ class DeviceRun(object):
         if getattr(self, 'handle', None) is not None and self.handle.value:
             self.lib.mk_solver_destroy(self.handle)
             self.handle = ctypes.c_void_p()
-        diag = self.precon if getattr(self, 'precon_kind', None) == 'diag' else None
-        for b in (self.d_rhs, self.d_guess, diag):
+        diags = [p for kind, p in self._slots() if kind == 'diag']
+        for b in [self.d_rhs, self.d_guess] + diags:
             if b is not None and not any(b is x for x in getattr(self, '_borrowed', [])):
                 b.free()
 

@@ -1,9 +1,7 @@
-import ctypes
-
 import numpy as np
 
 from .. import _lib
-from ..generic import KrylovMethod, DeviceRun, as_f64_vector
+from ..generic import KrylovMethod, DeviceRun, as_f64_vector, resolve_precon
 
 __docformat__ = 'restructuredtext'
 
@@ -29,7 +27,7 @@ class _LlsBase(KrylovMethod):
         self.normal_eqns_resids = []
         self.dir_errors_window = []
         self.iterates = []
-        self.precon_route = {'M': 'none', 'N': 'none'}       # how the last solve applied M and N (see _lls_precon)
+        self.precon_route = {'M': 'none', 'N': 'none'}       # how the last solve applied M and N (see generic.resolve_precon)
         self.msg = ['The exact solution is  x = 0                              ',
                     'Ax - b is small enough, given atol, btol                  ',
                     'The least-squares solution is good enough, given atol     ',
@@ -46,165 +44,43 @@ class _LlsBase(KrylovMethod):
         d = self.dir_errors_window
         return float(d[-1]) * float(np.sqrt(res.aux[3])) if len(d) and np.isfinite(d[-1]) else 0.0
 
-    def _lls_precon(self, P, size, which):
-        """How the device loop applies M / N (`u = M(Mu)`, `v = N(Nv)`: lsqr.py:190,202,254,266), resolved like
-        ``KrylovMethod._device_precon`` resolves ``precon``; returns ``(route, payload)`` with the route in the words of
-        ``DeviceRun.precon_kind``:
-
-        * ``'diag'``: an operator that exposes its diagonal (DiagonalOperator, linop.py:473-516) -- the fp64 array, applied
-          inside the kernels;
-        * ``'ilu'`` / ``'lbfgs'``: an incomplete factorization (`tools.ilu0` / `tools.ic0`) or an inverse L-BFGS operator,
-          applied on the device by its sweeps / two-loop chain;
-        * ``'cheb'``: a Chebyshev polynomial preconditioner (`tools.chebyshev`) of a symmetric matrix of that side's size,
-          applied on the device by its chain of products;
-        * ``'device'``: a CsrOperator, or an operator with a device view (`tools.block_jacobi`, block operators of device
-          matrices), square and of that side's size -- a product on the device;
-        * ``'host'``: any other callable, called back on the host at those sites."""
-        if P is None:
-            return 'none', None
-        name = self.__class__.__name__
-        diag = getattr(P, 'diag', None)
-        if diag is not None and not callable(diag):
-            return 'diag', as_f64_vector(diag, size, which + '.diag')
-        from ..tools import ChebyshevPreconditioner, IluPreconditioner
-        from ..lbfgs import InverseLBFGSOperator
-        from ..linop import CsrOperator
-        if isinstance(P, ChebyshevPreconditioner):
-            if tuple(P.shape) != (size, size):
-                raise ValueError('%s: %s has shape %s, expected %s' % (name, which, tuple(P.shape), (size, size)))
-            return 'cheb', P
-        is_ilu = isinstance(P, IluPreconditioner)
-        if is_ilu or (isinstance(P, InverseLBFGSOperator) and P._is_inverse):
-            if tuple(P.shape) != (size, size):
-                raise ValueError('%s: %s has shape %s, expected %s' % (name, which, tuple(P.shape), (size, size)))
-            return ('ilu' if is_ilu else 'lbfgs'), P
-        dev = P if isinstance(P, CsrOperator) else None
-        if dev is None and hasattr(P, '_device_view'):
-            dev = P._device_view()
-        if dev is not None and getattr(dev, 'local_size', None) is None:
-            if tuple(dev.shape) != (size, size):
-                raise ValueError('%s: %s has shape %s, expected %s' % (name, which, tuple(dev.shape), (size, size)))
-            return 'device', dev
-        if not callable(P) and not hasattr(P, '__mul__'):
-            raise TypeError('%s: %s must be callable (the reference evaluates `%s(vector)`); got a %s'
-                            % (name, which, which, type(P).__name__))
-        return 'host', P
-
-    @staticmethod
-    def _host_thunk(P, size, errors):
-        def call(user, ip, op_):
-            try:
-                vin = np.ctypeslib.as_array(ctypes.cast(ip, ctypes.POINTER(ctypes.c_double)), shape=(size,)).copy()
-                out = np.asarray(P(vin) if callable(P) else P * vin)
-                if out.shape != (size,):
-                    raise ValueError('preconditioner returned shape %s, expected (%d,)' % (out.shape, size))
-                np.ctypeslib.as_array(ctypes.cast(op_, ctypes.POINTER(ctypes.c_double)), shape=(size,))[:] = out
-                return 0
-            except BaseException as exc:                    # noqa: B902  (must not propagate through the C frames)
-                errors.append(exc)
-                return 1
-        return _lib.PRECON_FN(call)
-
-    def _run(self, rhs, itnlim, damp, atol, btol, conlim, M, N, kwargs, x_rows=False):
+    def _run(self, rhs, itnlim, damp, atol, btol, conlim, M, N, kwargs):
         A = self._device_operator()
+        m, n = A.shape
         # M and N: the reference calls them as functions, `u = M(Mu)`, `v = N(Nv)` (lsqr.py:190,202)
-        sides = (self._lls_precon(M, A.shape[0], 'M'), self._lls_precon(N, A.shape[1], 'N'))
+        name = self.__class__.__name__
+        sides = (resolve_precon(M, m, 'M', name), resolve_precon(N, n, 'N', name))
         self.precon_route = {'M': sides[0][0], 'N': sides[1][0]}
         if kwargs.get('wantvar', False):
             raise NotImplementedError('wantvar is broken in the reference as well (lsqr.py:155)')
-        m, n = A.shape
-        etol = kwargs.get('etol', 1.0e-6)
         window = kwargs.get('window', 5)
         store_iterates = kwargs.get('store_iterates', False)
+        table = kwargs.get('_table')                         # `show=True`: the reference's iteration log (see _ShowTable)
         b = as_f64_vector(np.asarray(rhs).squeeze()[:m], m, 'rhs')
         At = A.T
-        lib = _lib.init()
         self.iterates = []
-        # DeviceRun sizes its rhs buffer from the operator's input size: build the run by hand for m x n
-        d_rhs = _lib.DeviceArray.from_numpy(b)
-        p = _lib.MkParams()
-        p.struct_size = ctypes.sizeof(_lib.MkParams)
-        p.kind = self.kind
-        p.itnlim = int(itnlim)
-        p.damp, p.atol, p.btol, p.conlim, p.etol = float(damp), float(atol), float(btol), float(conlim), float(etol)
-        p.window = int(window)
-        handle = ctypes.c_void_p()
-        _lib.check(lib.mk_solver_create(A.handle, ctypes.byref(p), ctypes.byref(handle)))
-        cb_errors = []
-        cbs = [self._host_thunk(P, size, cb_errors) if route == 'host' else None
-               for (route, P), size in zip(sides, (m, n))]
-        d_diag = [_lib.DeviceArray.from_numpy(P) if route == 'diag' else None for route, P in sides]
-        try:
-            _lib.check(lib.mk_solver_set_transpose(handle, At.handle))
-            if cbs[0] is not None or cbs[1] is not None:
-                none = ctypes.cast(None, _lib.PRECON_FN)
-                _lib.check(lib.mk_solver_set_lls_precon_callback(handle, cbs[0] or none, None, cbs[1] or none, None))
-            if d_diag[0] is not None or d_diag[1] is not None:
-                _lib.check(lib.mk_solver_set_lls_precon(handle, None if d_diag[0] is None else d_diag[0].ptr,
-                                                        None if d_diag[1] is None else d_diag[1].ptr))
-            for side, (route, P) in enumerate(sides):       # (the solver holds what it is given until it is destroyed)
-                if route == 'device':
-                    _lib.check(lib.mk_solver_set_lls_precon_csr(handle, side, P.handle))
-                elif route == 'ilu':
-                    _lib.check(lib.mk_solver_set_lls_precon_ilu(handle, side, P._live()))
-                elif route == 'cheb':
-                    _lib.check(lib.mk_solver_set_lls_precon_cheb(handle, side, P._live()))
-                elif route == 'lbfgs':
-                    _lib.check(lib.mk_solver_set_lls_precon_bfgs(handle, side, P._live()))
-
-            def chk(rc):
-                if rc != 0 and hasattr(A, 'raise_pending'):
-                    A.raise_pending()                         # what a matrix-free operator raised in its callback
-                if rc != 0 and cb_errors:
-                    raise cb_errors[0]                        # ... or M / N in theirs
-                _lib.check(rc)
-            chk(lib.mk_solver_setup(handle, d_rhs.ptr, None))
-            res = _lib.MkResult()
-            _lib.check(lib.mk_solver_finish(handle, ctypes.byref(res)))
-            nx = m if x_rows else n
-
-            def get_x():
-                px = ctypes.c_void_p()
-                _lib.check(lib.mk_solver_x(handle, ctypes.byref(px)))
-                return _lib.download(px.value, nx)
+        # (no placement draws: they pay for CG's fused passes only)
+        with DeviceRun(A, self.kind, b, transpose=At, sides=[payload for _, payload in sides], placement_draws=1,
+                       itnlim=int(itnlim), damp=float(damp), atol=float(atol), btol=float(btol), conlim=float(conlim),
+                       etol=float(kwargs.get('etol', 1.0e-6)), window=int(window)) as run:
+            run.setup()
+            res = run.finish()
             if store_iterates:
-                self.iterates.append(get_x())
-            table = kwargs.get('_table')                     # `show=True`: the reference's iteration log (see _ShowTable)
-
-            def x_first():
-                px = ctypes.c_void_p()
-                _lib.check(lib.mk_solver_x(handle, ctypes.byref(px)))
-                v0 = ctypes.c_double()
-                _lib.check(lib.mk_memcpy_d2h(ctypes.byref(v0), px.value, 8))
-                return v0.value
+                self.iterates.append(run.x())
             if table is not None:
-                table.start(res, x_first())
+                table.start(res, run.x_first())
             while not res.halted:
-                done = ctypes.c_int64()
-                chk(lib.mk_solver_iterate(handle, 1 if (store_iterates or table is not None) else (1 << 20),
-                                          ctypes.byref(done)))
+                run.iterate(1 if (store_iterates or table is not None) else (1 << 20))
                 last_itn = int(res.itn)
-                _lib.check(lib.mk_solver_finish(handle, ctypes.byref(res)))
-                if store_iterates and int(res.itn) > last_itn:
-                    self.iterates.append(get_x())
+                res = run.finish()
+                advanced = int(res.itn) > last_itn
+                if store_iterates and advanced:
+                    self.iterates.append(run.x())
                 if table is not None:
-                    table.after_pass(res, x_first() if int(res.itn) > last_itn else None, int(res.itn) > last_itn)
-            x = get_x()
-            hist = np.empty(int(res.hist_len))
-            derr = np.empty(int(res.hist_len))
-            _lib.check(lib.mk_solver_history(handle, hist.ctypes.data, len(hist)))
-            _lib.check(lib.mk_solver_history2(handle, derr.ctypes.data, len(derr)))
-            r = None
-            if self.kind == _lib.MK_CRAIG:
-                pr = ctypes.c_void_p()
-                _lib.check(lib.mk_solver_vector(handle, 0, ctypes.byref(pr), None))
-                r = _lib.download(pr.value, m)
-        finally:
-            lib.mk_solver_destroy(handle)
-            d_rhs.free()
-            for buf in d_diag:
-                if buf is not None:
-                    buf.free()
+                    table.after_pass(res, run.x_first() if advanced else None, advanced)
+            x = run.x()
+            hist, derr = run.history(), run.history2()
+            r = run.vector(0) if self.kind == _lib.MK_CRAIG else None
         itn = int(res.itn)
         A._nMatvec += itn
         At._nMatvec += itn + (1 if res.residNorm0 > 0 else 0)
@@ -438,7 +314,7 @@ class CRAIGMRFramework(_LlsBase):
         m, n = getattr(self.A, 'global_shape', self.A.shape)
         if itnlim is None:
             itnlim = min([m, n])
-        res, x, _, itn = self._run(b, itnlim, damp, atol, btol, conlim, M, N, kwargs, x_rows=True)
+        res, x, _, itn = self._run(b, itnlim, damp, atol, btol, conlim, M, N, kwargs)
         istop = int(res.istop)
         if show:
             print(' ')

@@ -135,9 +135,7 @@ class Minres(KrylovMethod):
                     run.iterate(1 << 20)
                     res = run.finish()
             x = run.x()
-            hist = run.history()
-            derr = np.empty(len(hist))
-            _lib.check(run.lib.mk_solver_history2(run.handle, derr.ctypes.data, len(hist)))
+            hist, derr = run.history(), run.history2()
 
         istop, itn = int(res.istop), int(res.itn)
         rnorm, Arnorm, Anorm, Acond, ynorm = res.residNorm, res.Arnorm, res.Anorm, res.Acond, res.ynorm

@@ -102,7 +102,7 @@ def precons(case, m, n):
 
 
 def through_callbacks(kw, calls=None):
-    """The same objects behind plain functions: nothing `_lls_precon` recognises, so they are called back on the host."""
+    """The same objects behind plain functions: nothing `resolve_precon` recognises, so they are called back on the host."""
     def wrap(side, P):
         def call(v):
             if calls is not None:
@@ -435,3 +435,97 @@ def test_destroying_the_solver_releases_what_its_sides_hold():
     print("left after the solver went: %.1f MiB" % (left / 2.0**20))
     assert left < 8 << 20                                    # (the solver's own vectors went too: `left` may be negative)
     op.free()
+
+
+# ------------------------------------------------------------------ 6. one handle, every kind in turn
+KIND_ORDER = ("diag", "csr", "ilu", "lbfgs", "cheb", "callback", "none")
+
+
+def test_a_replaced_kind_leaves_nothing_behind():
+    """One BiCGSTAB handle (A = the 33-row tridiagonal matrix) and one LSQR handle (its first 17 columns; M and N both of the
+    kind) take every kind of preconditioner in turn and solve again after each replacement: x, both history channels and
+    itn are, byte for byte, those of a fresh handle that only ever held that kind.  Whatever a slot keeps across a
+    replacement -- its ones, the pointer the kernels multiply by, the pinned buffers, d_ptmp -- must not show.  The
+    lengths are odd, so the stream kernels' tail lane runs."""
+    from pykrylov_amd import _lib, tools
+    from pykrylov_amd.generic import HostPrecon
+    lib = _lib.init()
+    m, n = 33, 17
+    T = tridiag(m, 11)
+    rows = np.repeat(np.arange(m), np.diff(T.indptr))
+    keep = T.indices < n
+    A_sq, A_ls = op_from(T), op_from(csr_ref.from_coo(rows[keep], T.indices[keep], T.data[keep], (m, n)))
+    d_rhs = _lib.DeviceArray.from_numpy(T.matvec(np.ones(m)))
+    owned = [A_sq, A_ls, d_rhs]
+
+    def kit(k, seed, call_first):
+        """One preconditioner of every kind for vectors of k entries, as the C setters take them."""
+        P = op_from(tridiag(k, seed), symmetric=True)
+        d = _lib.DeviceArray.from_numpy(1.0 + np.random.default_rng(seed).random(k))
+        F, H, C = tools.ic0(P), make_precon("lbfgs", k, seed)[0], tools.chebyshev(P, degree=3)
+        host = HostPrecon(P, call_first)                     # (the callback: the same matrix, multiplied on the host)
+        owned.extend([C, F, H, d, P])
+        return {"diag": d.ptr, "csr": P.handle, "ilu": F._live(), "lbfgs": H._live(), "cheb": C._live(),
+                "callback": host.thunk(k), "none": None}
+    sq, pm, pn = kit(m, 1, False), kit(m, 2, True), kit(n, 3, True)
+
+    def attach_square(h, kind):
+        if kind == "callback":
+            return lib.mk_solver_set_precon_callback(h, sq[kind], None)
+        name = {"none": "csr"}.get(kind, kind)
+        return getattr(lib, "mk_solver_set_precon_" + name)(h, sq[kind])
+
+    def attach_sides(h, kind):
+        if kind == "diag":
+            return lib.mk_solver_set_lls_precon(h, pm[kind], pn[kind])
+        if kind == "callback":
+            return lib.mk_solver_set_lls_precon_callback(h, pm[kind], None, pn[kind], None)
+        setter = getattr(lib, "mk_solver_set_lls_precon_" + {"none": "csr", "lbfgs": "bfgs"}.get(kind, kind))
+        return setter(h, 0, pm[kind]) or setter(h, 1, pn[kind])
+
+    def create(op, transpose, **params):
+        prm = _lib.MkParams()
+        prm.struct_size = ctypes.sizeof(_lib.MkParams)
+        for k, v in params.items():
+            setattr(prm, k, v)
+        h = ctypes.c_void_p()
+        _lib.check(lib.mk_solver_create(op.handle, ctypes.byref(prm), ctypes.byref(h)))
+        if transpose:
+            _lib.check(lib.mk_solver_set_transpose(h, op.T.handle))
+        return h
+
+    def solve(h, nx):
+        _lib.check(lib.mk_solver_setup(h, d_rhs.ptr, None))
+        res = _lib.MkResult()
+        _lib.check(lib.mk_solver_finish(h, ctypes.byref(res)))
+        while not res.halted:
+            _lib.check(lib.mk_solver_iterate(h, 1 << 20, None))
+            _lib.check(lib.mk_solver_finish(h, ctypes.byref(res)))
+        px = ctypes.c_void_p()
+        _lib.check(lib.mk_solver_x(h, ctypes.byref(px)))
+        hist = np.zeros((2, int(res.hist_len)))
+        _lib.check(lib.mk_solver_history(h, hist[0].ctypes.data, hist.shape[1]))
+        _lib.check(lib.mk_solver_history2(h, hist[1].ctypes.data, hist.shape[1]))
+        return int(res.itn), int(res.nMatvec), bits(_lib.download(px.value, nx)), bits(hist)
+
+    families = (("bicgstab", attach_square, m, lambda: create(A_sq, False, kind=_lib.MK_BICGSTAB, abstol=1.0e-12,
+                                                                    reltol=1.0e-12, matvec_max=4 * m)),
+                ("lsqr", attach_sides, n, lambda: create(A_ls, True, kind=_lib.MK_LSQR, itnlim=3 * n, atol=1.0e-12,
+                                                         btol=1.0e-12, conlim=1.0e8, etol=0.0, window=5)))
+    for family, attach, nx, new_handle in families:
+        want = {}
+        for kind in KIND_ORDER:                              # fresh handles: each only ever holds its kind
+            h = new_handle()
+            _lib.check(attach(h, kind))
+            want[kind] = solve(h, nx)
+            _lib.check(lib.mk_solver_destroy(h))
+        # (the kinds do differ -- but for the callback, which applies the matrix of "csr")
+        assert len(set(want.values())) >= 6, family
+        h = new_handle()
+        for kind in KIND_ORDER:                              # one handle: every kind replaces the one before
+            _lib.check(attach(h, kind))
+            got = solve(h, nx)
+            print(family, kind, "itn", got[0], "nMatvec", got[1])
+            assert got[0] > 0 and got == want[kind], (family, kind)
+        _lib.check(lib.mk_solver_destroy(h))
+    free_all(owned)
