@@ -524,6 +524,32 @@ MK_API int mk_lbfgs_download(const mk_lbfgs *F, double *s_host, double *y_host);
  * solver's operator carries an exchange plan), MK_ERR_ARG on a size mismatch.  Call before mk_solver_setup.  A pair stored
  * between two solves is seen by the next one. */
 MK_API int mk_solver_set_precon_lbfgs(mk_solver *s, const mk_lbfgs *F);
+/* m = min(steps, nrows) steps of the symmetric Lanczos process on a square, SYMMETRIC device matrix A (the caller vouches
+ * for the symmetry), without reorthogonalisation: the tridiagonal T_m = tridiag(beta_j, alpha_j, beta_{j+1}) whose extreme
+ * eigenvalues estimate those of A (scale_diag != 0: of D^-1/2 A D^-1/2, D = diag(A), through the diagonally preconditioned
+ * recurrence) -- the interval of mk_cheb_create from the matrix instead of the Gershgorin bound.  The recurrence, every
+ * operation rounded on its own, in this order:
+ *     r2 = start_dev (n doubles, 16-byte aligned), or when NULL r2[i] = u(i, seed) - 1.0 with u the splitmix64 cell field of
+ *     mk_csr_poisson3d_varcoef;   y = r2 (scaled: y = dinv * r2, dinv[r] = 1.0 / a_rr);   beta_1 = sqrt(<r2, y>)
+ *     step j = 1..m:   s = 1.0 / beta_j;  v = s * y;  t = A v;  j > 1: t = t - (beta_j / beta_{j-1}) * r1;
+ *                      alpha_j = <v, t>;  ynew = (-alpha_j / beta_j) * r2 + t;  r1 = r2;  r2 = ynew;
+ *                      y = r2 (scaled: dinv * r2);  beta_{j+1} = sqrt(<r2, y>)
+ * <v, t> is summed in the order of a dot fused into the product kernel, <r2, y> in that of a stream kernel.  Two launches
+ * per step (a storage format that cuts a product into several launches adds its own) plus at most three; all scalars stay
+ * on the device until one download at the end, the work vectors are allocated in the call and freed before it returns.
+ * The run stops on the device after step j when beta_{j+1} is not > 2^-26 * max_{i<=j}(|alpha_i| + [i>1] * beta_i)
+ * (breakdown: every Ritz value is then an eigenvalue to sqrt(eps)), or when alpha_j or beta_{j+1} is not finite.
+ * Output, with `done` the steps completed: alpha_host[0 .. done) = alpha_1.., beta_host[0 .. done] = beta_1.. (beta_1 is
+ * the norm of the start vector and no entry of T); the arrays hold min(steps, nrows) and min(steps, nrows) + 1 doubles.
+ * info[k] for k < min(cap, MK_LANCZOS_INFO_LEN): 0 steps completed, 1 launches, 2 device bytes used, 3 elapsed time (us),
+ * 4 whether a scalar was not finite.
+ * MK_ERR_ARG for a non-square matrix, steps < 1, a matrix without rows, beta_1 zero or not finite, an alpha or beta that is
+ * not finite (the message gives the step) and -- with scale_diag -- a row whose diagonal entry is missing, zero or negative
+ * (the message names the smallest such row).  MK_ERR_UNSUPPORTED for operators that hold no arrays of their own and for
+ * operators with an exchange plan. */
+#define MK_LANCZOS_INFO_LEN 5
+MK_API int mk_csr_lanczos(const mk_csr *A, int32_t steps, int32_t scale_diag, uint64_t seed, const double *start_dev,
+                          double *alpha_host, double *beta_host, int64_t *info, int32_t cap);
 /* Chebyshev polynomial preconditioner z = p_k(A) r of a square, SYMMETRIC device matrix A (the caller vouches for the
  * symmetry): the Chebyshev iteration for A z = r from z = 0 on an interval [lmin, lmax], 0 < lmin < lmax, that should hold
  * A's spectrum (Saad, Iterative Methods, Alg. 12.1); with scale_diag != 0 the iteration for D^-1 A z = D^-1 r, D = diag(A).

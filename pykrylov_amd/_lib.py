@@ -37,6 +37,7 @@ MK_ILU_INFO_LEN = 12      # entries of mk_ilu_info (include/mikrylov.h)
 MK_LBFGS_INFO_LEN = 12    # entries of mk_lbfgs_info
 MK_CHEB_INFO_LEN = 8      # entries of mk_cheb_info
 MK_CHEB_MAX_DEGREE = 64   # highest degree of mk_cheb_create
+MK_LANCZOS_INFO_LEN = 5   # entries of mk_csr_lanczos' info
 
 MK_ROW_SCALE, MK_ROW_ADD, MK_ROW_SUB, MK_ROW_RSUB, MK_ROWPROG_MAX = 1, 2, 3, 4, 4
 
@@ -157,6 +158,7 @@ PROTOTYPES = {
     "mk_cheb_info": (ctypes.c_int, [c_vp, P(c_i64), c_i32]),
     "mk_cheb_coefficients": (ctypes.c_int, [c_vp, P(c_f64)]),
     "mk_solver_set_precon_cheb": (ctypes.c_int, [c_vp, c_vp]),
+    "mk_csr_lanczos": (ctypes.c_int, [c_vp, c_i32, c_i32, ctypes.c_uint64, c_vp, P(c_f64), P(c_f64), P(c_i64), c_i32]),
     "mk_solver_set_lls_precon_callback": (ctypes.c_int, [c_vp, PRECON_FN, c_vp, PRECON_FN, c_vp]),
     "mk_solver_set_lls_precon": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mk_solver_set_lls_precon_csr": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),

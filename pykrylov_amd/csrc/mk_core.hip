@@ -881,14 +881,8 @@ extern "C" int mk_csr_poisson3d(int64_t nx, int64_t ny, int64_t nz, int64_t row_
 // the neighbour exists and of k(c) itself where it does not (the coefficient of the boundary face): strictly
 // diagonally dominant on boundary rows, SPD, and practically every stored value distinct -- no value dictionary, no
 // constant-coefficient shortcut applies: this is the matrix that exercises the CSR product proper.  NumPy twin in
-// the test infrastructure: csr_ref.poisson3d_varcoef (bit-identical arrays, tests/test_gpu_varcoef.py).
-__host__ __device__ static inline double mk_cell_field(int64_t c, uint64_t seed) {
-    uint64_t z = ((uint64_t)c + 1ULL) * 0x9E3779B97F4A7C15ULL + seed;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z = z ^ (z >> 31);
-    return 0.5 + (double)(z >> 11) * 0x1.0p-53;
-}
+// the test infrastructure: csr_ref.poisson3d_varcoef (bit-identical arrays, tests/test_gpu_varcoef.py).  (mk_cell_field:
+// mk_internal.h -- the Lanczos start vector of mk_lanczos.hip is the same hash.)
 
 __global__ __launch_bounds__(MK_BLOCK) void gen_poisson3d_varcoef(int64_t nx, int64_t ny, int64_t nz, uint64_t seed,
                                                                   int64_t r_begin, int64_t r_end, int32_t *indptr,

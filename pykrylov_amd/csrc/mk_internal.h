@@ -246,6 +246,16 @@ static inline int mk_grid_spmv(int64_t ntiles) {
 // --------------------------------------------------------------------------------------
 #ifdef __HIPCC__
 
+// k(c) = 0.5 + u(c), u a 53-bit uniform from a splitmix64 hash of the cell number c: the coefficient field of the
+// variable-coefficient generators (mk_core.hip) and, less one, the default start vector of mk_csr_lanczos (mk_lanczos.hip)
+__host__ __device__ static inline double mk_cell_field(int64_t c, uint64_t seed) {
+    uint64_t z = ((uint64_t)c + 1ULL) * 0x9E3779B97F4A7C15ULL + seed;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    z = z ^ (z >> 31);
+    return 0.5 + (double)(z >> 11) * 0x1.0p-53;
+}
+
 // Sum over the workgroup, identical value returned to every thread.  Fixed tree:
 // shuffle-down 32,16,8,4,2,1 inside each wave64, then the four wave sums added in wave order.
 __device__ __forceinline__ double mk_block_sum(double v, double *s4) {

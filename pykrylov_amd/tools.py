@@ -250,15 +250,15 @@ class IluPreconditioner(LinearOperator):
 
 
 
-def _cheb_operator(op):
-    """Kind / shape checks of `chebyshev`, made before the device is touched (those of ``_ilu_operator(symmetric=True)``)."""
-    what = 'chebyshev'
+def _cheb_operator(op, what='chebyshev', noun='the Chebyshev preconditioner'):
+    """Kind / shape checks of `chebyshev` and `lanczos`, made before the device is touched (those of
+    ``_ilu_operator(symmetric=True)``)."""
     shape = getattr(op, 'shape', None)
     if shape is None or len(shape) != 2:
         raise TypeError('%s needs an operator with a `.shape`; got %r' % (what, type(op).__name__))
     from .linop import CsrOperator
     if getattr(op, 'local_size', None) is not None:
-        raise NotImplementedError('%s: the operator is row-partitioned; the Chebyshev preconditioner is single-GPU' % what)
+        raise NotImplementedError('%s: the operator is row-partitioned; %s is single-GPU' % (what, noun))
     if not isinstance(op, CsrOperator):
         raise TypeError('%s: %r holds no CSR arrays on the device; form its matrix (e.g. `to_csr_arrays()` of a device '
                         'operator) and wrap it in a CsrOperator' % (what, type(op).__name__))
@@ -269,7 +269,75 @@ def _cheb_operator(op):
     return op
 
 
-def chebyshev(op, degree=4, lmin=None, lmax=None, ratio=30.0, scale_diag=False):
+def _lanczos_args(what, steps, seed):
+    """`steps` and `seed` of `lanczos` (and of ``chebyshev(interval='lanczos')``), checked before the device is touched."""
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or int(steps) < 1 or int(steps) >= 2 ** 31:
+        raise ValueError('%s: steps must be a positive integer, got %r' % (what, steps))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError('%s: seed must be an integer from 0 to 2**64 - 1, got %r' % (what, seed))
+    return int(steps), int(seed)
+
+
+class LanczosResult(object):
+    """What `lanczos` returns.  `alpha` (alpha_1 .. alpha_m) and `beta` (beta_1 .. beta_{m+1}; beta_1 is the norm of the
+    start vector and no entry of T) as the device computed them, `steps` = m as done, `ritz` the eigenvalues of the m x m
+    tridiagonal T in ascending order, ``residuals[i] = |beta_{m+1} S[m-1, i]|`` with S the eigenvectors of T (the residual
+    norm of Ritz pair i), ``bounds = (ritz[0], ritz[-1] + residuals[-1])`` -- the upper end is the k-step Lanczos bound of
+    Zhou and Li for the largest eigenvalue --, and `info` (steps, launches, bytes, elapsed_us, nonfinite)."""
+
+    def __init__(self, alpha, beta, info):
+        self.alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+        self.beta = np.ascontiguousarray(beta, dtype=np.float64)
+        self.steps = m = len(self.alpha)
+        self.info = info
+        # a small dense host solve, like the compact form of L-BFGS: no LAPACK in the library
+        T = np.diag(self.alpha) + np.diag(self.beta[1:m], 1) + np.diag(self.beta[1:m], -1)
+        self.ritz, S = np.linalg.eigh(T)
+        self.residuals = np.abs(self.beta[m] * S[m - 1, :])
+        self.bounds = (float(self.ritz[0]), float(self.ritz[-1] + self.residuals[-1]))
+
+    def __repr__(self):
+        return 'LanczosResult(steps=%d, bounds=(%.6g, %.6g))' % ((self.steps,) + self.bounds)
+
+
+def lanczos(op, steps=10, scale_diag=False, seed=1, start=None):
+    """``min(steps, n)`` steps of the symmetric Lanczos process on a symmetric device matrix (a :class:`CsrOperator` declared
+    ``symmetric=True``), run ON the device (mk_csr_lanczos: the product kernel with ``<v, A v>`` fused and one stream kernel
+    per step, the scalars downloaded once at the end), as a spectrum estimate: a :class:`LanczosResult` whose `bounds` are
+    an interval for `chebyshev`.  ``scale_diag=True`` estimates the spectrum of ``D^-1/2 A D^-1/2`` (every row must store a
+    positive diagonal entry; MkError naming the row otherwise), which is that of the ``D^-1 A`` a scaled `chebyshev` iterates
+    on.  The start vector is `start` (n finite numbers) or, by default, a hashed vector of `seed` -- on purpose not a vector
+    of ones, which is orthogonal to the top eigenvector of ``poisson2d(m)`` for even m.  The run stops early at a breakdown
+    (`steps` then reads less than asked for: the Ritz values are eigenvalues).  No reorthogonalisation; do not go below the
+    default of 10 steps for an upper bound that is to hold."""
+    _cheb_operator(op, 'lanczos', 'the Lanczos estimate')
+    steps, seed = _lanczos_args('lanczos', steps, seed)
+    n = int(op.shape[0])
+    if n == 0:
+        raise ValueError('lanczos: the operator has no rows')
+    if start is not None:
+        start = np.ascontiguousarray(start, dtype=np.float64)
+        if start.shape != (n,):
+            raise ValueError('lanczos: start must have %d entries, got shape %s' % (n, start.shape))
+        if not np.all(np.isfinite(start)) or not np.any(start):
+            raise ValueError('lanczos: start must be finite and not zero')
+    lib = _lib.init()
+    m = min(steps, n)
+    alpha, beta = (ctypes.c_double * m)(), (ctypes.c_double * (m + 1))()
+    v = (ctypes.c_int64 * _lib.MK_LANCZOS_INFO_LEN)()
+    d_start = _lib.DeviceArray.from_numpy(start) if start is not None else None
+    try:
+        _lib.check(lib.mk_csr_lanczos(op.handle, steps, int(bool(scale_diag)), seed, d_start.ptr if d_start else None,
+                                      alpha, beta, v, _lib.MK_LANCZOS_INFO_LEN))
+    finally:
+        if d_start is not None:
+            d_start.free()
+    info = dict(zip(('steps', 'launches', 'bytes', 'elapsed_us', 'nonfinite'), (int(x) for x in v)))
+    done = info['steps']
+    return LanczosResult(alpha[:done], beta[:done + 1], info)
+
+
+def chebyshev(op, degree=4, lmin=None, lmax=None, ratio=30.0, scale_diag=False, interval='gershgorin', steps=10, seed=1):
     """Chebyshev polynomial preconditioner ``z = p_k(A) r`` of a symmetric device matrix (a :class:`CsrOperator` declared
     ``symmetric=True``) as a DEVICE preconditioner: `degree` = k steps of the Chebyshev iteration for ``A z = r`` from
     ``z = 0`` on the interval ``[lmin, lmax]`` (Saad, Alg. 12.1), each step ONE product of `op` in the storage format it has,
@@ -279,8 +347,18 @@ def chebyshev(op, degree=4, lmin=None, lmax=None, ratio=30.0, scale_diag=False):
     convention of hypre and Ifpack2 where no lower estimate is given).  ``scale_diag=True`` runs the iteration on
     ``D^-1 A`` (Jacobi scaling; every row must store a nonzero diagonal, MkError naming the row otherwise) -- the operator is
     then symmetric in the D inner product only.  ``1 <= degree <= 64``.  Passed as ``precon=`` to BiCGSTAB / CGS / TFQMR /
-    MINRES / SYMMLQ, or as ``M=`` / ``N=`` to the least-squares solvers, it is applied without a host round trip."""
+    MINRES / SYMMLQ, or as ``M=`` / ``N=`` to the least-squares solvers, it is applied without a host round trip.
+
+    ``interval='lanczos'`` takes whichever of `lmin` and `lmax` is not given from ``lanczos(op, steps, scale_diag,
+    seed).bounds`` instead -- an interval from the matrix: the smallest Ritz value, and the largest plus its residual norm (an
+    under-estimated `lmax` is the dangerous end: the residual polynomial grows without bound beyond it; an over-estimated
+    `lmin` leaves the preconditioner positive definite).  ValueError if the smallest Ritz value is not positive; where the
+    Krylov space held one eigenvalue only, ``lmin = lmax / ratio``.  It costs `steps` products and stream passes once, and is
+    not always the better interval, hence opt-in.  `interval_source` of the result names, per end, where it
+    came from: ``'gershgorin'``, ``'lanczos'`` or ``'given'``."""
     _cheb_operator(op)
+    if interval not in ('gershgorin', 'lanczos'):
+        raise ValueError("chebyshev: interval must be 'gershgorin' or 'lanczos', got %r" % (interval,))
     if isinstance(degree, bool) or not isinstance(degree, (int, np.integer)):
         raise ValueError('chebyshev: degree must be an integer from 1 to %d, got %r' % (_lib.MK_CHEB_MAX_DEGREE, degree))
     if not 1 <= int(degree) <= _lib.MK_CHEB_MAX_DEGREE:
@@ -292,15 +370,38 @@ def chebyshev(op, degree=4, lmin=None, lmax=None, ratio=30.0, scale_diag=False):
         raise ValueError('chebyshev: the interval needs 0 < lmin < lmax, got lmin = %r, lmax = %r' % (lmin, lmax))
     if lmin is None and not (np.isfinite(ratio) and ratio > 1):
         raise ValueError('chebyshev: ratio must be finite and > 1, got %r' % (ratio,))
-    return ChebyshevPreconditioner(op, int(degree), lmin, lmax, float(ratio), bool(scale_diag))
+    source = tuple(interval if v is None else 'given' for v in (lmin, lmax))
+    estimate = None
+    if interval == 'lanczos':
+        if lmin is not None and lmax is not None:
+            raise ValueError("chebyshev: interval='lanczos' with lmin and lmax both given leaves nothing to estimate")
+        steps, seed = _lanczos_args('chebyshev', steps, seed)
+        estimate = lanczos(op, steps, scale_diag, seed)
+        if not estimate.ritz[0] > 0:
+            raise ValueError('chebyshev: the smallest Ritz value of %d Lanczos steps is %r: the matrix is not positive '
+                             'definite' % (estimate.steps, float(estimate.ritz[0])))
+        lo, hi = estimate.bounds
+        if lmax is None:
+            lmax = hi
+        if lmin is None:
+            # (a Krylov space of one eigenvalue: no lower estimate)
+            lmin = lo if lo < hi * (1.0 - 2.0 ** -26) else float(lmax) / float(ratio)
+        if not lmin < lmax:
+            raise ValueError('chebyshev: the interval needs 0 < lmin < lmax, got lmin = %r, lmax = %r (Lanczos bounds %r)'
+                             % (lmin, lmax, (lo, hi)))
+    M = ChebyshevPreconditioner(op, int(degree), lmin, lmax, float(ratio), bool(scale_diag))
+    M.interval_source = source
+    M.lanczos = estimate
+    return M
 
 
 class ChebyshevPreconditioner(LinearOperator):
     """``p_k(A)`` of a symmetric device matrix, resident in HBM (`chebyshev`).  ``self * v`` applies it to a NumPy vector,
     `apply_device` to DeviceArray vectors; solvers given it as ``precon=`` (``M=`` / ``N=``) apply it on the device
     (mk_solver_set_precon_cheb / mk_solver_set_lls_precon_cheb).  Attributes: `degree`, `interval` (``(lmin, lmax)`` as
-    used), `coefficients` (``c0`` and the arrays ``c1``, ``c2`` of the steps), `scaled`, `info` (mk_cheb_info as a dict).
-    `free()` releases this object's reference; a solver that still applies the object keeps it alive."""
+    used), `interval_source` (per end ``'gershgorin'``, ``'lanczos'`` or ``'given'``), `lanczos` (the :class:`LanczosResult`
+    behind ``interval='lanczos'``, else None), `coefficients` (``c0`` and the arrays ``c1``, ``c2`` of the steps), `scaled`,
+    `info` (mk_cheb_info as a dict).  `free()` releases this object's reference; a solver that still applies the object keeps it alive."""
 
     def __init__(self, op, degree, lmin, lmax, ratio, scale_diag):
         lib = _lib.init()
@@ -310,6 +411,8 @@ class ChebyshevPreconditioner(LinearOperator):
         self._n = int(op.shape[0])
         self.degree = int(degree)
         self.scaled = bool(scale_diag)
+        self.interval_source = tuple('gershgorin' if v is None else 'given' for v in (lmin, lmax))
+        self.lanczos = None
         if lmin is None and lmax is not None:
             lmin = float(lmax) / ratio
         elif lmin is None and ratio != 30.0:
