@@ -369,8 +369,11 @@ typedef enum {
     MK_LSQR = 7,      /* pykrylov/lls/lsqr.py:86-453          */
     MK_LSMR = 8,      /* pykrylov/lls/lsmr.py:64-492          */
     MK_CRAIG = 9,     /* pykrylov/lls/craig.py:104-520        */
-    MK_CRAIGMR = 10   /* pykrylov/lls/craigmr.py:51-241       */
+    MK_CRAIGMR = 10,  /* pykrylov/lls/craigmr.py:51-241       */
+    MK_GMRES = 11     /* restarted GMRES(m), right preconditioned (no reference module): a square solver */
 } mk_solver_kind;
+
+#define MK_GMRES_MAX_RESTART 128
 
 typedef struct {
     int32_t struct_size;      /* = sizeof(mk_params) */
@@ -390,6 +393,8 @@ typedef struct {
     double atol;              /* lsqr.py:86 */
     double btol;              /* lsqr.py:86 */
     double conlim;            /* lsqr.py:87 */
+    int32_t restart;          /* MK_GMRES: steps per cycle, 1 .. MK_GMRES_MAX_RESTART (clamped to n); MK_ERR_ARG otherwise */
+    int32_t reorth;           /* MK_GMRES: 1 = classical Gram-Schmidt twice per step, 0 = once */
 } mk_params;
 
 typedef struct {
@@ -406,11 +411,15 @@ typedef struct {
     double residNorm0;
     double threshold;
     double Anorm, Acond, Arnorm, ynorm, xnorm;
-    double aux[8];
+    double aux[8];            /* MK_GMRES: [0] restarts, [1] steps of the last cycle, [2] bytes of the basis */
 } mk_result;
 
 typedef struct mk_solver mk_solver;
 
+/* MK_GMRES: restarted GMRES(m) with right preconditioning (mk_params.restart, .reorth), every preconditioner setter of the
+ * square solvers, single GPU: MK_ERR_UNSUPPORTED for an operator with an exchange plan or a row block, MK_ERR_ARG for a
+ * restart outside 1 .. MK_GMRES_MAX_RESTART.  The basis (min(restart, n) + 1 vectors) is allocated at the first set-up;
+ * x is complete after every mk_solver_iterate call that observed the halt (the cycle in progress is closed then). */
 MK_API int mk_solver_create(const mk_csr *A, const mk_params *params, mk_solver **out);
 MK_API int mk_solver_destroy(mk_solver *s);
 /* The least-squares solvers (MK_LSQR ... MK_CRAIGMR) need `A.T * u` (lls/lsqr.py:200,264): hand them the
@@ -435,8 +444,9 @@ MK_API int mk_solver_set_precon_diag(mk_solver *s, const double *diag);
  * each preconditioner site the vector is copied to the host, the callback runs, and the inner product that involves
  * its result is formed on the device afterwards.  Not invoked once the loop has halted; in BiCGSTAB / CGS / TFQMR the
  * application that precedes a product happens before that product's loop test, so the callback may run once more
- * than in the reference (its last result is unused).  The six square solvers; MK_ERR_UNSUPPORTED for the lls kinds
- * and on partitioned operators.  Replaces a diagonal set earlier.  Call before mk_solver_setup. */
+ * than in the reference (its last result is unused; MK_GMRES applies it after the stop test: once per step and once
+ * per cycle end).  The six square solvers and MK_GMRES; MK_ERR_UNSUPPORTED for the lls kinds and on partitioned
+ * operators.  Replaces a diagonal set earlier.  Call before mk_solver_setup. */
 typedef int (*mk_precon_fn)(void *user, const double *r_host, double *y_host);
 MK_API int mk_solver_set_precon_callback(mk_solver *s, mk_precon_fn fn, void *user);
 /* ... or a DEVICE operator: `precon * r` (generic/generic.py:76) evaluated as a product with a device matrix or

@@ -18,13 +18,16 @@ P = ctypes.POINTER
 
 MK_CG, MK_BICGSTAB, MK_CGS, MK_TFQMR, MK_MINRES, MK_SYMMLQ = 1, 2, 3, 4, 5, 6
 MK_LSQR, MK_LSMR, MK_CRAIG, MK_CRAIGMR = 7, 8, 9, 10
+MK_GMRES = 11
+MK_GMRES_MAX_RESTART = 128
 
 
 class MkParams(ctypes.Structure):
     _fields_ = [("struct_size", c_i32), ("kind", c_i32), ("abstol", c_f64), ("reltol", c_f64),
                 ("matvec_max", c_i64), ("check_curvature", c_i32), ("has_shift", c_i32), ("shift", c_f64),
                 ("rtol", c_f64), ("etol", c_f64), ("itnlim", c_i64), ("window", c_i32), ("spmv_event_stride", c_i32),
-                ("damp", c_f64), ("atol", c_f64), ("btol", c_f64), ("conlim", c_f64)]
+                ("damp", c_f64), ("atol", c_f64), ("btol", c_f64), ("conlim", c_f64),
+                ("restart", c_i32), ("reorth", c_i32)]
 
 
 class MkRowOp(ctypes.Structure):

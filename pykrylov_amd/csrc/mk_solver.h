@@ -207,6 +207,7 @@ mk_solver *mk_make_tfqmr();
 mk_solver *mk_make_minres();
 mk_solver *mk_make_symmlq();
 mk_solver *mk_make_lls(int kind);
+mk_solver *mk_make_gmres();
 
 #ifdef __HIPCC__
 // ------------------------------------------------------------------ small shared kernels

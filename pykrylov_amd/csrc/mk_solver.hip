@@ -6,7 +6,7 @@ int mk_solver::init_common(const mk_csr *A_, const mk_params *p) {
     A->dependents += 1;              // (borrowed for the solver's lifetime: destroying A meanwhile is deferred)
     prm = *p;
     n = A->ex.mode >= 0 ? A->ex.n_local : A->nrows;
-    const bool rectangular_ok = prm.kind >= MK_LSQR;
+    const bool rectangular_ok = prm.kind >= MK_LSQR && prm.kind <= MK_CRAIGMR;
     slot[0].len = n;
     slot[1].len = rectangular_ok ? A->ncols : 0;
     if (rectangular_ok && A->ex.mode >= 0)
@@ -303,6 +303,15 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
         case MK_LSMR:
         case MK_CRAIG:
         case MK_CRAIGMR: s = mk_make_lls(params->kind); break;
+        case MK_GMRES:
+            if (params->restart < 1 || params->restart > MK_GMRES_MAX_RESTART)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: GMRES restart = %d, must be 1 .. %d", (int)params->restart,
+                               MK_GMRES_MAX_RESTART);
+            if (A->ex.mode >= 0 || A->row_block)
+                return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: the operator is row-partitioned (it carries an exchange "
+                               "plan or a row block); GMRES is single-GPU");
+            s = mk_make_gmres();
+            break;
         default: break;
     }
     if (!s) return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: solver kind %d is not available", params->kind);
