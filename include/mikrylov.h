@@ -597,11 +597,53 @@ MK_API int mk_cheb_coefficients(const mk_cheb *F, double *host);
  * the preconditioner is replaced; NULL removes it.  Single GPU, MK_ERR_ARG on a size mismatch.  Call before
  * mk_solver_setup. */
 MK_API int mk_solver_set_precon_cheb(mk_solver *s, const mk_cheb *F);
+/* FSAI (factorized sparse approximate inverse, Kolotilina and Yeremin) of a square, symmetric positive definite device
+ * matrix A ~ L L': a sparse lower-triangular G ~ L^-1 on a fixed pattern, computed on the device; the preconditioner is
+ * M^-1 = G' G.  A owns CSR arrays with sorted rows and no duplicates (as for mk_ilu0_create); it is read during the call only
+ * and not borrowed afterwards.
+ * The pattern: pat_indptr_host / pat_indices_host (n + 1 and pat_indptr_host[n] host ints), or both NULL for the stored
+ * lower triangle of A, diagonal included (extracted on the device).  A given pattern is lower triangular, every row sorted
+ * without duplicates and ending with its diagonal entry; no row has more than MK_FSAI_MAX_ROW entries.
+ * Row i with pattern columns P[0] < ... < P[m-1] = i, one rounding per operation, every sum sequential in the order written
+ * (so the result does not depend on how rows and entries are assigned to lanes):
+ *     gather    S[a][b] = A[P[a], P[b]] for b <= a, read from the lower part of row P[a] of A; a position A does not store
+ *               counts as 0.0
+ *     Cholesky  s = S[a][b]; for k = 0 .. b-1: s = s - L[a][k] * L[b][k];  L[a][a] = sqrt(s);  L[a][b] = s / L[b][b]
+ *     solve     y[m-1] = 1.0 / L[m-1][m-1];  for a = m-1 .. 0: s = y[a] (0.0 for a < m-1);
+ *               for k = m-1 .. a+1: s = s - L[k][a] * y[k];  y[a] = s / L[a][a]
+ *     scaling   g = y / sqrt(y[m-1])            (then diag(G A G') = 1)
+ * G and G' (mk_csr_transpose of G) are kept as device matrices and get the storage formats their patterns earn.
+ * MK_ERR_ARG for a non-square matrix, a row of A without a stored diagonal entry (pattern from A), a pattern that is not as
+ * described (the message names the first bad row), a pattern row that is longer than MK_FSAI_MAX_ROW (the message names the
+ * row and its length) and a diagonal s of a Cholesky factor that is not > 0 or not finite (the message names the smallest
+ * such row).  MK_ERR_UNSUPPORTED for operators that hold no arrays of their own and for operators with an exchange plan. */
+typedef struct mk_fsai mk_fsai;
+#define MK_FSAI_MAX_ROW 32
+MK_API int mk_fsai_create(const mk_csr *A, const int32_t *pat_indptr_host, const int32_t *pat_indices_host, mk_fsai **out);
+/* Destroying an object that solvers still hold (mk_solver_set_precon_fsai) is deferred until the last of them goes. */
+MK_API int mk_fsai_destroy(mk_fsai *F);
+/* out = G' (G in) on device vectors (in == out allowed; out of place, `in` is not modified): two products, tmp = G in and
+ * out = G' tmp, each a row sum from left to right in whatever storage format the matrix has.  Enqueued on the library's
+ * stream. */
+MK_API int mk_fsai_apply(const mk_fsai *F, const double *in_dev, double *out_dev);
+/* info[k] for k < min(cap, MK_FSAI_INFO_LEN): 0 rows, 1 nonzeros of G, 2 longest row of G, 3 launches per apply (2; a storage
+ * format that cuts a product into several launches adds its own), 4 device bytes held (the CSR arrays of G and G' and one
+ * vector; not what their storage formats add), 5 / 6 storage format of G / of G' (built by this call if need be), 7 set-up
+ * time (us). */
+#define MK_FSAI_INFO_LEN 8
+MK_API int mk_fsai_info(const mk_fsai *F, int64_t *info, int32_t cap);
+/* G as CSR arrays to the host: rows + 1 ints, nnz ints, nnz doubles (info 0 and 1); a NULL array is skipped. */
+MK_API int mk_fsai_download(const mk_fsai *F, int32_t *indptr_host, int32_t *indices_host, double *values_host);
+/* The two matrices the object owns, borrowed (for mk_csr_set_format / mk_csr_format_info; never destroy them); either
+ * pointer may be NULL. */
+MK_API int mk_fsai_factors(const mk_fsai *F, mk_csr **G, mk_csr **Gt);
+/* ... and as the preconditioner of the square solvers, exactly like mk_solver_set_precon_cheb. */
+MK_API int mk_solver_set_precon_fsai(mk_solver *s, const mk_fsai *F);
 /* The least-squares kinds take two preconditioners, applied by the reference as `u = M(Mu)` in the m-space and
  * `v = N(Nv)` in the n-space of the Golub-Kahan process (lls/lsqr.py:189-190,201-202,253-254,265-266 and the same
  * lines of lsmr.py, craig.py, craigmr.py).  Each side holds ONE preconditioner of any of the kinds the square solvers
  * take -- a diagonal, a host callback, a device matrix or composite, an incomplete factorization, an inverse L-BFGS
- * operator, a Chebyshev polynomial preconditioner -- and every setter below replaces what its side held (releasing the reference it kept on a matrix or object)
+ * operator, a Chebyshev polynomial preconditioner, an FSAI preconditioner -- and every setter below replaces what its side held (releasing the reference it kept on a matrix or object)
  * without touching the other side.  MK_ERR_UNSUPPORTED for the six square solvers.  Call before mk_solver_setup.
  *
  * Diagonals: device arrays with the diagonals of M (nrows(A) entries) and N (ncols(A) entries), multiplied inside the
@@ -624,6 +666,7 @@ MK_API int mk_solver_set_lls_precon_callback(mk_solver *s, mk_precon_fn fn_m, vo
  *           next one.  (Spelt _bfgs on purpose: the names that contain "lbfgs" are the operator's own entry points and the
  *           square solvers' mk_solver_set_precon_lbfgs, a closed set that tests/test_lbfgs_cpu.py pins name by name.)
  *   _cheb:  a Chebyshev polynomial preconditioner (mk_cheb_create) of a symmetric matrix of that side's size.
+ *   _fsai:  an FSAI preconditioner (mk_fsai_create) of a symmetric positive definite matrix of that side's size.
  * The solver holds a factor or operator until it is destroyed or the side is given something else: destroying the object
  * meanwhile is deferred.  NULL removes what the side holds.  MK_ERR_ARG on a size mismatch or a non-square matrix.
  * Single GPU: with row blocks over several GPUs (mk_csr_set_row_block) only diagonals are supported, mk_solver_setup fails
@@ -633,6 +676,7 @@ MK_API int mk_solver_set_lls_precon_csr(mk_solver *s, int side, const mk_csr *P)
 MK_API int mk_solver_set_lls_precon_ilu(mk_solver *s, int side, const mk_ilu *F);
 MK_API int mk_solver_set_lls_precon_bfgs(mk_solver *s, int side, const mk_lbfgs *F);
 MK_API int mk_solver_set_lls_precon_cheb(mk_solver *s, int side, const mk_cheb *F);
+MK_API int mk_solver_set_lls_precon_fsai(mk_solver *s, int side, const mk_fsai *F);
 /* Everything before the `while` loop of the reference's solve().  rhs_dev has n_local
  * entries; guess_dev may be NULL (x0 = 0).  Neither is modified. */
 MK_API int mk_solver_setup(mk_solver *s, const double *rhs_dev, const double *guess_dev);

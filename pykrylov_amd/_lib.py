@@ -41,6 +41,8 @@ MK_LBFGS_INFO_LEN = 12    # entries of mk_lbfgs_info
 MK_CHEB_INFO_LEN = 8      # entries of mk_cheb_info
 MK_CHEB_MAX_DEGREE = 64   # highest degree of mk_cheb_create
 MK_LANCZOS_INFO_LEN = 5   # entries of mk_csr_lanczos' info
+MK_FSAI_INFO_LEN = 8      # entries of mk_fsai_info
+MK_FSAI_MAX_ROW = 32      # longest pattern row of mk_fsai_create
 
 MK_ROW_SCALE, MK_ROW_ADD, MK_ROW_SUB, MK_ROW_RSUB, MK_ROWPROG_MAX = 1, 2, 3, 4, 4
 
@@ -161,6 +163,13 @@ PROTOTYPES = {
     "mk_cheb_info": (ctypes.c_int, [c_vp, P(c_i64), c_i32]),
     "mk_cheb_coefficients": (ctypes.c_int, [c_vp, P(c_f64)]),
     "mk_solver_set_precon_cheb": (ctypes.c_int, [c_vp, c_vp]),
+    "mk_fsai_create": (ctypes.c_int, [c_vp, c_vp, c_vp, P(c_vp)]),
+    "mk_fsai_destroy": (ctypes.c_int, [c_vp]),
+    "mk_fsai_apply": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mk_fsai_info": (ctypes.c_int, [c_vp, P(c_i64), c_i32]),
+    "mk_fsai_download": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "mk_fsai_factors": (ctypes.c_int, [c_vp, P(c_vp), P(c_vp)]),
+    "mk_solver_set_precon_fsai": (ctypes.c_int, [c_vp, c_vp]),
     "mk_csr_lanczos": (ctypes.c_int, [c_vp, c_i32, c_i32, ctypes.c_uint64, c_vp, P(c_f64), P(c_f64), P(c_i64), c_i32]),
     "mk_solver_set_lls_precon_callback": (ctypes.c_int, [c_vp, PRECON_FN, c_vp, PRECON_FN, c_vp]),
     "mk_solver_set_lls_precon": (ctypes.c_int, [c_vp, c_vp, c_vp]),
@@ -168,6 +177,7 @@ PROTOTYPES = {
     "mk_solver_set_lls_precon_ilu": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
     "mk_solver_set_lls_precon_bfgs": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
     "mk_solver_set_lls_precon_cheb": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
+    "mk_solver_set_lls_precon_fsai": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
     "mk_solver_setup": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "mk_solver_iterate": (ctypes.c_int, [c_vp, c_i64, P(c_i64)]),
     "mk_solver_finish": (ctypes.c_int, [c_vp, P(MkResult)]),

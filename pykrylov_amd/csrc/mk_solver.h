@@ -31,7 +31,8 @@ int mk_exchange_begin(const mk_csr *A, double *x_ext);     // may leave the mess
 int mk_exchange_wait(const mk_csr *A, hipStream_t stream); // ... until here
 
 // A device object that applies out = P in under the loop's halt words: the incomplete factorizations (mk_ilu.hip), the
-// inverse L-BFGS operator (mk_lbfgs.hip) and the Chebyshev polynomial preconditioner (mk_cheb.hip).  A solver that applies it holds it; destroying it meanwhile is deferred to the
+// inverse L-BFGS operator (mk_lbfgs.hip), the Chebyshev polynomial preconditioner (mk_cheb.hip) and the FSAI preconditioner
+// (mk_fsai.hip).  A solver that applies it holds it; destroying it meanwhile is deferred to the
 // last release.  The destructor of the derived object frees its device memory.
 struct MkDeviceOp {
     int64_t n = 0;                 // rows
@@ -63,7 +64,7 @@ enum MkPreconKind {
                            // pinned buffers
     MK_PRECON_CSR,         // mk_solver_set_precon_csr / _lls_precon_csr: a device matrix or composite `op` (counted in
                            // op->dependents), e.g. the inverted diagonal blocks of block-Jacobi; the product stays in HBM
-    MK_PRECON_OBJECT       // mk_solver_set_precon_ilu / _lbfgs / _cheb, mk_solver_set_lls_precon_ilu / _bfgs / _cheb: a held
+    MK_PRECON_OBJECT       // mk_solver_set_precon_ilu / _lbfgs / _cheb / _fsai, mk_solver_set_lls_precon_ilu / _bfgs / _cheb / _fsai: a held
                            // MkDeviceOp `obj`
 };
 

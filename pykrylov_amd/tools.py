@@ -492,3 +492,162 @@ class ChebyshevPreconditioner(LinearOperator):
 
     def __del__(self):
         self.free()
+
+
+def _pattern_power(indptr, indices, n, power):
+    """``(indptr, indices)`` of the lower triangle of the pattern of ``A**power`` (`power` >= 2), the symbolic product formed
+    on the host with NumPy: the pairs (i, k) with k in row j of A for every (i, j) held so far, made unique by sorting
+    their keys ``i * n + k``.  Rows come out sorted."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    cols = np.asarray(indices, dtype=np.int64)
+    length = np.diff(indptr)
+    bi, bj = np.repeat(np.arange(n, dtype=np.int64), length), cols
+    for step in range(power - 1):
+        cnt = length[bj]
+        first = np.cumsum(cnt) - cnt
+        pos = np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(first, cnt) + np.repeat(indptr[bj], cnt)
+        ii, kk = np.repeat(bi, cnt), cols[pos]
+        if step == power - 2:                                # (the last product: only the lower triangle is wanted)
+            low = kk <= ii
+            ii, kk = ii[low], kk[low]
+        key = np.unique(ii * n + kk)
+        bi, bj = key // n, key % n
+    ip = np.zeros(n + 1, dtype=np.int64)
+    ip[1:] = np.cumsum(np.bincount(bi, minlength=n))
+    return ip, bj
+
+
+def fsai(op, power=1, pattern=None):
+    """FSAI preconditioner (factorized sparse approximate inverse, Kolotilina and Yeremin) of a symmetric positive definite
+    device matrix (a :class:`CsrOperator` declared ``symmetric=True``) as a DEVICE preconditioner: for ``A ~ L L^T`` a sparse
+    lower-triangular ``G ~ L^-1`` on a fixed pattern, computed on the GPU by one small dense SPD solve per row (all rows
+    independent: no level schedule), and ``M^-1 = G^T G`` -- an apply is two sparse products through the library's product
+    kernels and storage formats.
+
+    The pattern of G is the lower triangle of the pattern of ``A**power``, `power` = 1 (the default: the stored lower triangle
+    of `op`, extracted on the device), 2 or 3.  For ``power > 1`` the symbolic product is a HOST set-up step: it is formed
+    with NumPy from ``op.to_csr_arrays()``, once (a device symbolic product is not available).  ``pattern=(indptr,
+    indices)`` gives the pattern explicitly instead (lower triangular, every row sorted, without duplicates and ending with
+    its diagonal entry); it excludes ``power != 1``.  No row of the pattern may hold more than 32 entries: ValueError naming
+    the row otherwise.  Passed as ``precon=`` to CG / BiCGSTAB / CGS / TFQMR / MINRES / SYMMLQ / GMRES, or as ``M=`` / ``N=``
+    to the least-squares solvers, it is applied without a host round trip.  Raises MkError naming the row for a pattern that
+    is not as described, a row without a stored diagonal entry and a breakdown (the matrix is not positive definite)."""
+    _cheb_operator(op, 'fsai', 'the FSAI preconditioner')
+    if isinstance(power, bool) or not isinstance(power, (int, np.integer)) or not 1 <= int(power) <= 3:
+        raise ValueError('fsai: power must be 1, 2 or 3, got %r' % (power,))
+    power = int(power)
+    n = int(op.shape[0])
+    if pattern is not None:
+        if power != 1:
+            raise ValueError('fsai: give either `pattern` or `power`, not both (got power = %d with a pattern)' % power)
+        try:
+            ip, ix = pattern
+        except (TypeError, ValueError):
+            raise ValueError('fsai: pattern must be a pair (indptr, indices)')
+        ip, ix = np.asarray(ip), np.asarray(ix)
+        if ip.ndim != 1 or ix.ndim != 1 or ip.dtype.kind not in 'iu' or ix.dtype.kind not in 'iu':
+            raise ValueError('fsai: pattern must be a pair of 1-D integer arrays (indptr, indices)')
+        if ip.shape != (n + 1,) or int(ip[0]) != 0 or int(ip[-1]) != ix.size or ix.size >= 2 ** 31:
+            raise ValueError('fsai: pattern indptr must have %d entries, start at 0 and end at len(indices) = %d'
+                             % (n + 1, ix.size))
+        if ix.size and not (0 <= int(ix.min()) and int(ix.max()) < n):
+            raise ValueError('fsai: pattern indices must lie in 0 .. %d' % (n - 1))
+    elif power > 1:
+        indptr, indices, _ = op.to_csr_arrays()
+        ip, ix = _pattern_power(indptr, indices, n, power)
+    if pattern is not None or power > 1:
+        length = np.diff(ip)
+        if length.size and int(length.max()) > _lib.MK_FSAI_MAX_ROW:
+            row = int(np.argmax(length > _lib.MK_FSAI_MAX_ROW))
+            raise ValueError('fsai: row %d of the pattern has %d entries, more than %d: lower `power` (or give a sparser '
+                             '`pattern`)' % (row, int(length[row]), _lib.MK_FSAI_MAX_ROW))
+        pattern = (np.ascontiguousarray(ip, dtype=np.int32), np.ascontiguousarray(ix, dtype=np.int32))
+    return FsaiPreconditioner(op, power, pattern)
+
+
+class FsaiPreconditioner(LinearOperator):
+    """``G^T G`` of an FSAI factor resident in HBM (`fsai`).  ``self * v`` applies it to a NumPy vector, `apply_device` to
+    DeviceArray vectors; solvers given it as ``precon=`` (``M=`` / ``N=``) apply it on the device
+    (mk_solver_set_precon_fsai / mk_solver_set_lls_precon_fsai).  Attributes: `power`, `info` (mk_fsai_info as a dict).
+    `factor_arrays()` downloads G.  The object does not keep the matrix it was computed from.  `free()` releases this
+    object's reference; a solver that still applies the object keeps it alive."""
+
+    def __init__(self, op, power=1, pattern=None):
+        lib = _lib.init()
+        self._lib = lib
+        self._handle = None
+        self._buf = None
+        self._n = int(op.shape[0])
+        self.power = int(power)
+        h = ctypes.c_void_p()
+        ip, ix = (None, None) if pattern is None else pattern
+        rc = lib.mk_fsai_create(op.handle, None if ip is None else ip.ctypes.data, None if ix is None else ix.ctypes.data,
+                                ctypes.byref(h))
+        if rc != 0:
+            msg = lib.mk_last_error().decode(errors='replace')
+            if 'more than MK_FSAI_MAX_ROW' in msg:           # (the pattern came from the device: power = 1)
+                raise ValueError('fsai: %s: lower `power` (or give a sparser `pattern`)' % msg.split(': ', 1)[-1])
+            _lib.check(rc)
+        self._handle = h.value
+        LinearOperator.__init__(self, self._n, self._n, matvec=self._apply, symmetric=True, dtype=np.float64)
+
+    handle = property(lambda self: self._live(), doc="Opaque ``mk_fsai*`` for libmikrylov.")
+
+    @property
+    def info(self):
+        names = ('rows', 'nnz', 'longest_row', 'launches', 'bytes', 'format_g', 'format_gt', 'setup_us')
+        v = (ctypes.c_int64 * _lib.MK_FSAI_INFO_LEN)()
+        _lib.check(self._lib.mk_fsai_info(self._live(), v, _lib.MK_FSAI_INFO_LEN))
+        return dict(zip(names, (int(x) for x in v)))
+
+    def _live(self):
+        if not self._handle:
+            raise ValueError('the FSAI preconditioner has been freed')
+        return self._handle
+
+    def _apply(self, r):
+        h = self._live()
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if self._buf is None:
+            self._buf = _lib.DeviceArray(self._n, zero=False)
+        self._buf.upload(r)
+        _lib.check(self._lib.mk_fsai_apply(h, self._buf.ptr, self._buf.ptr))
+        return self._buf.to_numpy()
+
+    def apply_device(self, d_in, d_out):
+        "``d_out = G^T (G d_in)`` on DeviceArray vectors (`d_in is d_out` allowed); enqueued on the library's stream."
+        for d in (d_in, d_out):
+            if not isinstance(d, _lib.DeviceArray) or d.n != self._n or d.dtype != np.float64 or not d.ptr:
+                raise ValueError('apply_device needs live float64 DeviceArray vectors of %d entries' % self._n)
+        _lib.check(self._lib.mk_fsai_apply(self._live(), d_in.ptr, d_out.ptr))
+
+    def factor_arrays(self):
+        "``(indptr, indices, values)`` of G: lower triangular CSR, every row ending with its diagonal entry."
+        h = self._live()
+        nnz = self.info['nnz']
+        indptr = np.empty(self._n + 1, dtype=np.int32)
+        indices = np.empty(nnz, dtype=np.int32)
+        values = np.empty(nnz, dtype=np.float64)
+        _lib.check(self._lib.mk_fsai_download(h, indptr.ctypes.data, indices.ctypes.data, values.ctypes.data))
+        return indptr, indices, values
+
+    def factor_handles(self):
+        """Borrowed ``mk_csr*`` handles of G and of its transpose, for ``mk_csr_set_format`` / ``mk_csr_format_info``; they
+        belong to this object."""
+        g, gt = ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.check(self._lib.mk_fsai_factors(self._live(), ctypes.byref(g), ctypes.byref(gt)))
+        return g.value, gt.value
+
+    def free(self):
+        if getattr(self, '_buf', None) is not None:
+            self._buf.free()
+            self._buf = None
+        if getattr(self, '_handle', None):
+            try:
+                self._lib.mk_fsai_destroy(self._handle)
+            except Exception:
+                pass
+            self._handle = None
+
+    def __del__(self):
+        self.free()
