@@ -370,10 +370,12 @@ typedef enum {
     MK_LSMR = 8,      /* pykrylov/lls/lsmr.py:64-492          */
     MK_CRAIG = 9,     /* pykrylov/lls/craig.py:104-520        */
     MK_CRAIGMR = 10,  /* pykrylov/lls/craigmr.py:51-241       */
-    MK_GMRES = 11     /* restarted GMRES(m), right preconditioned (no reference module): a square solver */
+    MK_GMRES = 11,    /* restarted GMRES(m), right preconditioned (no reference module): a square solver */
+    MK_IDR = 12       /* IDR(s), right preconditioned (no reference module): a square solver */
 } mk_solver_kind;
 
 #define MK_GMRES_MAX_RESTART 128
+#define MK_IDR_MAX_S 32
 
 typedef struct {
     int32_t struct_size;      /* = sizeof(mk_params) */
@@ -412,6 +414,8 @@ typedef struct {
     double threshold;
     double Anorm, Acond, Arnorm, ynorm, xnorm;
     double aux[8];            /* MK_GMRES: [0] restarts, [1] steps of the last cycle, [2] bytes of the basis */
+                              /* MK_IDR: [0] the s in use (after clamping to n), [1] completed cycles, [2] bytes of P, G and U,
+                               * [3] breakdown: 0 none, 1 a zero or non-finite pivot M[k,k], 2 a zero or non-finite om */
 } mk_result;
 
 typedef struct mk_solver mk_solver;
@@ -426,6 +430,15 @@ MK_API int mk_solver_destroy(mk_solver *s);
  * transposed matrix (mk_csr_transpose) before mk_solver_setup.  rhs then has nrows(A) entries and x
  * ncols(A) (CRAIG-MR: nrows(A), craigmr.py:112). */
 MK_API int mk_solver_set_transpose(mk_solver *s, const mk_csr *At);
+/* MK_IDR: IDR(s) in its biorthogonal form with right preconditioning, every preconditioner setter of the square solvers,
+ * single GPU: mk_solver_create returns MK_ERR_UNSUPPORTED for an operator with an exchange plan or a row block.  This
+ * setter carries its arguments; call it before mk_solver_setup (MK_ERR_STATE afterwards: P, G and U, 3 s vectors, are
+ * sized at the first set-up).  `shadow_dim` is s, 1 .. MK_IDR_MAX_S (MK_ERR_ARG otherwise), clamped to n.  `shadow` is
+ * NULL -- row k of P is then the hashed field of `seed` + k with entries in [-0.5, 0.5), filled on the device -- or a
+ * borrowed device array of shadow_dim * n doubles stored row after row, copied at the first set-up (shadow_dim > n is
+ * refused there).  Without the call s = 4 and seed = 1.  MK_ERR_UNSUPPORTED on another solver kind.  A pivot or an om that
+ * is zero or not finite halts the run (mk_result.aux[3]); x is the last iterate then, as after every step. */
+MK_API int mk_solver_set_idr(mk_solver *s, int32_t shadow_dim, uint64_t seed, const double *shadow);
 /* Several GPUs: mark `A` as THIS rank's block of consecutive rows of a taller m x n operator (its columns are global
  * and unlocalized; no mk_csr_set_exchange).  The least-squares solvers then keep every m-space vector (rhs, u, r;
  * x of CRAIG-MR) sliced like the rows and every n-space vector (v, w, x) whole on every rank: `A * v` needs no
@@ -445,7 +458,7 @@ MK_API int mk_solver_set_precon_diag(mk_solver *s, const double *diag);
  * its result is formed on the device afterwards.  Not invoked once the loop has halted; in BiCGSTAB / CGS / TFQMR the
  * application that precedes a product happens before that product's loop test, so the callback may run once more
  * than in the reference (its last result is unused; MK_GMRES applies it after the stop test: once per step and once
- * per cycle end).  The six square solvers and MK_GMRES; MK_ERR_UNSUPPORTED for the lls kinds and on partitioned
+ * per cycle end; MK_IDR likewise, once per product).  The six square solvers, MK_GMRES and MK_IDR; MK_ERR_UNSUPPORTED for the lls kinds and on partitioned
  * operators.  Replaces a diagonal set earlier.  Call before mk_solver_setup. */
 typedef int (*mk_precon_fn)(void *user, const double *r_host, double *y_host);
 MK_API int mk_solver_set_precon_callback(mk_solver *s, mk_precon_fn fn, void *user);

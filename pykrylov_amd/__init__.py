@@ -16,6 +16,7 @@ from .bicgstab import BiCGSTAB                                                  
 from .cgs import CGS                                                                            # noqa: F401
 from .tfqmr import TFQMR                                                                        # noqa: F401
 from .gmres import GMRES                                                                        # noqa: F401
+from .idr import IDR                                                                            # noqa: F401
 from .minres import Minres                                                                      # noqa: F401
 from .symmlq import Symmlq                                                                      # noqa: F401
 from .lbfgs import InverseLBFGSOperator, LBFGSOperator, CompactLBFGSOperator                    # noqa: F401

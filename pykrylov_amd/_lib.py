@@ -20,6 +20,8 @@ MK_CG, MK_BICGSTAB, MK_CGS, MK_TFQMR, MK_MINRES, MK_SYMMLQ = 1, 2, 3, 4, 5, 6
 MK_LSQR, MK_LSMR, MK_CRAIG, MK_CRAIGMR = 7, 8, 9, 10
 MK_GMRES = 11
 MK_GMRES_MAX_RESTART = 128
+MK_IDR = 12
+MK_IDR_MAX_S = 32
 
 
 class MkParams(ctypes.Structure):
@@ -135,6 +137,7 @@ PROTOTYPES = {
     "mk_solver_create": (ctypes.c_int, [c_vp, P(MkParams), P(c_vp)]),
     "mk_solver_destroy": (ctypes.c_int, [c_vp]),
     "mk_solver_set_transpose": (ctypes.c_int, [c_vp, c_vp]),
+    "mk_solver_set_idr": (ctypes.c_int, [c_vp, c_i32, ctypes.c_uint64, c_vp]),
     "mk_csr_set_row_block": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "mk_solver_set_precon_diag": (ctypes.c_int, [c_vp, c_vp]),
     "mk_solver_set_precon_callback": (ctypes.c_int, [c_vp, PRECON_FN, c_vp]),

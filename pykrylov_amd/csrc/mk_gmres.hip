@@ -21,11 +21,11 @@
 // (-ffp-contract=off); every dot has the lanes, the grid and the tree of mk_stream_kernel<MkOpDot>, then mk_total.
 #include <cmath>
 
+#include "mk_multicol.h"      // GM_GROUP, GmCols and D, the many-column dot
 #include "mk_solver.h"
 
 namespace {
 
-constexpr int GM_GROUP = 8;                         // basis columns per launch of D, U and C
 constexpr int GM_MAXR = MK_GMRES_MAX_RESTART;
 
 // the shared scalar file (poll() brings it to the host)
@@ -35,40 +35,6 @@ enum { S_THRESH = 0, S_RESID = 1, S_RESID0 = 2, S_BETA = 3, S_HN = 4, S_J = 5, S
 struct GmScal {
     double *h, *r, *c, *s, *g, *y;
     int m;
-};
-
-struct GmCols {
-    const double *col[GM_GROUP];
-};
-
-// D: partial sums of <v_i, w> for the columns c0 .. c0 + ncol - 1 into the slots c0 + c of a bank (`partials` of the launch
-// points at slot c0).  Per column the additions of MkOpDot in its order.
-struct GmOpMultiDot {
-    static constexpr int NACC = GM_GROUP, SLOT0 = 0;
-    const double *w;
-    GmCols v;
-    int ncol;
-    __device__ bool prologue(double *, bool) { return false; }
-    __device__ bool skip() const { return false; }
-    __device__ void pair(int64_t i, double *acc) {
-        const double2 wv = mk_ld2(w, i);
-        double2 cv[GM_GROUP];
-#pragma unroll
-        for (int c = 0; c < GM_GROUP; ++c)
-            if (c < ncol) cv[c] = mk_ld2(v.col[c], i);
-#pragma unroll
-        for (int c = 0; c < GM_GROUP; ++c)
-            if (c < ncol) {
-                acc[c] += cv[c].x * wv.x;
-                acc[c] += cv[c].y * wv.y;
-            }
-    }
-    __device__ void one(int64_t i, double *acc) {
-        const double wv = w[i];
-#pragma unroll
-        for (int c = 0; c < GM_GROUP; ++c)
-            if (c < ncol) acc[c] += v.col[c][i] * wv;
-    }
 };
 
 // U: w = w - h_c v_c for the columns of one group, ascending, each term a multiply and a subtraction; h_c is the total of

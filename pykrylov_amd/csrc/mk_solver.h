@@ -209,6 +209,7 @@ mk_solver *mk_make_minres();
 mk_solver *mk_make_symmlq();
 mk_solver *mk_make_lls(int kind);
 mk_solver *mk_make_gmres();
+mk_solver *mk_make_idr();
 
 #ifdef __HIPCC__
 // ------------------------------------------------------------------ small shared kernels

@@ -312,6 +312,12 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
                                "plan or a row block); GMRES is single-GPU");
             s = mk_make_gmres();
             break;
+        case MK_IDR:
+            if (A->ex.mode >= 0 || A->row_block)
+                return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: the operator is row-partitioned (it carries an exchange "
+                               "plan or a row block); IDR is single-GPU");
+            s = mk_make_idr();
+            break;
         default: break;
     }
     if (!s) return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: solver kind %d is not available", params->kind);

@@ -224,9 +224,12 @@ class DeviceRun(object):
         self.precon_kind, self.precon, self.sides = 'none', None, None
         # `transpose`: the device operator A.T the least-squares kinds need (mk_solver_set_transpose); their rhs has
         # nrows(A) entries.  `sides`: their M and N, a pair of `resolve_precon` payloads.  `placement_draws`: see _draws().
+        # `idr`: (s, seed, shadow) of mk_solver_set_idr, the shadow vectors None or an (s, n) fp64 array.
         transpose = params.pop('transpose', None)
         sides = params.pop('sides', None)
         draws = params.pop('placement_draws', None)
+        self.idr = params.pop('idr', None)
+        self._d_shadow = None
         if draws is not None:
             self.placement_draws = int(draws)
         n = getattr(op, 'local_size', None) or (op.shape[0] if transpose is not None else op.shape[1])
@@ -255,6 +258,8 @@ class DeviceRun(object):
             self._borrowed += [p for p in (precon_diag,) + tuple(sides or ()) if isinstance(p, _lib.DeviceArray)]
             self.precon_kind, self.precon, self._precon_arg = self._resolve_precon(precon_diag, n)
             self.sides = None if sides is None else [self._resolve_precon(p, k) for p, k in zip(sides, op.shape)]
+            if self.idr is not None and self.idr[2] is not None:
+                self._d_shadow = _lib.DeviceArray.from_numpy(np.ascontiguousarray(self.idr[2], dtype=np.float64))
             self._apply_precon(self.handle)
         except Exception:
             self.lib.mk_solver_destroy(self.handle)
@@ -351,6 +356,9 @@ class DeviceRun(object):
         lib = self.lib
         if self.transpose is not None:
             _lib.check(lib.mk_solver_set_transpose(handle, self.transpose.handle))
+        if self.idr is not None:
+            _lib.check(lib.mk_solver_set_idr(handle, int(self.idr[0]), int(self.idr[1]),
+                                             None if self._d_shadow is None else self._d_shadow.ptr))
         if self.precon_kind != 'none':
             setter = {'host': 'callback', 'device': 'csr'}.get(self.precon_kind, self.precon_kind)
             user = (None,) if self.precon_kind == 'host' else ()
@@ -499,7 +507,7 @@ class DeviceRun(object):
             self.lib.mk_solver_destroy(self.handle)
             self.handle = ctypes.c_void_p()
         diags = [p for kind, p in self._slots() if kind == 'diag']
-        for b in [self.d_rhs, self.d_guess] + diags:
+        for b in [self.d_rhs, self.d_guess, getattr(self, '_d_shadow', None)] + diags:
             if b is not None and not any(b is x for x in getattr(self, '_borrowed', [])):
                 b.free()
 
