@@ -652,11 +652,86 @@ MK_API int mk_fsai_download(const mk_fsai *F, int32_t *indptr_host, int32_t *ind
 MK_API int mk_fsai_factors(const mk_fsai *F, mk_csr **G, mk_csr **Gt);
 /* ... and as the preconditioner of the square solvers, exactly like mk_solver_set_precon_cheb. */
 MK_API int mk_solver_set_precon_fsai(mk_solver *s, const mk_fsai *F);
+/* Smoothed-aggregation algebraic multigrid (Vanek, Mandel, Brezina) of a square, SYMMETRIC device matrix A with a positive
+ * stored diagonal (the caller vouches for the symmetry): the hierarchy is set up on the device, an apply is one V(1,1)-cycle.
+ * A owns CSR arrays with sorted rows and no duplicates; the object borrows it (A may be destroyed meanwhile: it lives on until
+ * the object goes).  Every operation is rounded on its own and every sum is sequential in the order written, formed by one
+ * lane, so the hierarchy does not depend on grids, on atomics or on `expand_cap`.  Per level, A_0 = A:
+ *   1 diagonal, bound   d_i = the first stored a_ii;  dinv_i = 1.0 / d_i;  lmax = max_i (sum_j |a_ij|) / |a_ii|, the row added
+ *                       left to right in stored order from 0.0 -- the Gershgorin bound of mk_cheb_create(scale_diag = 1).  The
+ *                       level's smoother S is mk_cheb_create(A_l, degree, lmax / ratio, lmax, 1).
+ *   2 strength          a stored entry v = a_ij, j != i, v != 0 is strong iff  v * v > ((theta * theta) * d_i) * d_j.
+ *   3 MIS(2) roots      (Bell, Dalton, Olson 2012)  key_i = state << 62 | h30(i) << 32 | i, state 2 in / 1 undecided / 0 out,
+ *                       every node undecided at first.  h30(i) = z >> 34 with z the splitmix64 word of the cell field of
+ *                       mk_csr_poisson3d_varcoef for cell i:  z = (i + 1) * 0x9E3779B97F4A7C15 + seed (mod 2^64);
+ *                       z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  z = z ^ z >> 31.
+ *                       Only i and `seed` feed it: the same on every level.  A round: m1_i = max(key_i, key_j over the strong
+ *                       entries of row i), m2_i = the same of m1 (each from one buffer into another); then an undecided node
+ *                       with m2_i == key_i goes in, one whose m2_i has state 2 goes out.  Rounds repeat until a device
+ *                       counter of undecided nodes, read by the host once per round, is zero.
+ *   4 aggregates        the roots (state 2) are numbered in index order by an exclusive scan (on the device).  Pass 1: a root
+ *                       takes its number; another node takes the number of the root among its strong entries with the largest
+ *                       |a_ij|, the first in stored order on ties; else -1.  Pass 2, reading pass 1's buffer: a node left at
+ *                       -1 takes pass 1's value of the strong entry with the largest |a_ij| among those pass 1 assigned, the
+ *                       first on ties.  A node without strong entries is a root and a singleton.
+ *   5 prolongator       P = T - (omega / lmax) D^-1 (A T), T[i, agg(i)] = 1.0.  Row i is the list (agg(i), 1.0), then
+ *                       (agg(j), (-((omega / lmax) * dinv_i)) * a_ij) over the stored entries of row i in order; the list is
+ *                       stable-sorted by column and duplicates are summed in list order from 0.0 (the rule of
+ *                       mk_csr_from_coo).  R = mk_csr_transpose(P).
+ *   6 Galerkin product  A_{l+1} = R (A_l P), two products C = X Y: row i of C is the list (j, x_ik * y_kj) over the entries of
+ *                       row i of X in order and within each over the entries of row k of Y in order, compressed as above.  The
+ *                       lists are expanded in chunks of whole rows of at most `expand_cap` entries (a longer row alone;
+ *                       0 = 2^26 entries, 24 bytes each while a chunk is compressed; at most 2^31 - 1).
+ *   7 stopping          no further level when n_l <= coarse_max, when the hierarchy has max_levels levels, or when a level
+ *                       has as many aggregates as rows.
+ *   8 coarsest level    n <= coarse_max: downloaded, factored on the host by the Cholesky recurrence of mk_fsai_create over
+ *                       the dense lower triangle (s = a[a][b]; k = 0 .. b-1: s = s - L[a][k] * L[b][k]; L[a][a] = sqrt(s),
+ *                       L[a][b] = s / L[b][b]), then column c of the inverse:  a = 0 .. n-1: s = (a == c ? 1.0 : 0.0);
+ *                       k = 0 .. a-1: s = s - L[a][k] * y[k]; y[a] = s / L[a][a];  a = n-1 .. 0: s = y[a]; k = n-1 .. a+1:
+ *                       s = s - L[k][a] * x[k]; x[a] = s / L[a][a];  Ainv[a][c] = x[a].  Uploaded as a dense matrix.  A pivot
+ *                       that is not positive and finite, or a larger last level: the level is solved by its smoother alone.
+ * The cycle on level l, with S the level's mk_cheb_apply:  x = S(b);  r = b - A x;  b_{l+1} = R r;  e = cycle(l + 1, b_{l+1});
+ * x = x + P e;  r = b - A x;  x = x + S(r).  On the coarsest level x = Ainv b, each row summed left to right from 0.0 (or
+ * x = S(b)).  Residual and correction are row epilogues of the products of A_l and P in whatever storage format the matrices
+ * have; R r is a plain product.
+ * 1 <= degree <= MK_CHEB_MAX_DEGREE, ratio > 1, omega > 0, theta >= 0, 1 <= coarse_max <= MK_AMG_MAX_COARSE,
+ * 1 <= max_levels <= MK_AMG_MAX_LEVELS, 0 <= expand_cap < 2^31: MK_ERR_ARG otherwise, for a non-square matrix and for a row,
+ * on any level, whose diagonal entry is missing, zero, negative or not finite (the message names the smallest such row and the
+ * level).  MK_ERR_UNSUPPORTED for operators that hold no arrays of their own and for operators with an exchange plan. */
+typedef struct mk_amg mk_amg;
+#define MK_AMG_MAX_LEVELS 16
+#define MK_AMG_MAX_COARSE 1024
+MK_API int mk_amg_create(const mk_csr *A, double theta, int32_t degree, double ratio, double omega, int32_t coarse_max,
+                         int32_t max_levels, uint64_t seed, int64_t expand_cap, mk_amg **out);
+/* Destroying an object that solvers still hold (mk_solver_set_precon_amg) is deferred until the last of them goes. */
+MK_API int mk_amg_destroy(mk_amg *F);
+/* out = one V(1,1)-cycle on in, device vectors (in == out allowed; out of place, `in` is not modified).  Enqueued on the
+ * library's stream. */
+MK_API int mk_amg_apply(const mk_amg *F, const double *in_dev, double *out_dev);
+/* info[k] for k < min(cap, MK_AMG_INFO_LEN).  level = -1, the totals: 0 levels, 1 device bytes held (the levels' CSR arrays, P, R,
+ * vectors, smoothers, the coarse inverse; not what storage formats add), 2 set-up time (us), 3 launches per apply ((7 + 2 degree)
+ * per level but the last, 1 or 1 + degree on the last; a storage format that cuts a product into several launches adds its own),
+ * 4 the coarsest level is solved by 1 the dense inverse, 0 its smoother alone, 5 operator complexity x 1000 (sum of nnz(A_l) /
+ * nnz(A_0), rounded), 6 grid complexity x 1000, 7 sum of nnz(A_l), 8 sum of the levels' rows, 9 why there is no inverse: 0 there is
+ * one, 1 the last level has more than coarse_max rows, 2 a pivot was not positive.
+ * level >= 0: 0 rows, 1 nnz of A_l, 2 nnz of P (0 on the last level), 3 aggregates, 4 MIS(2) rounds, 5 / 6 entries of the expanded
+ * lists of A P / of R (A P), 7 / 8 chunks they took, 9 chunks of P's list. */
+#define MK_AMG_INFO_LEN 10
+MK_API int mk_amg_info(const mk_amg *F, int32_t level, int64_t *info, int32_t cap);
+/* A matrix of a level, borrowed (for mk_csr_download / mk_csr_set_format / mk_csr_format_info; never destroy it): which = 0 A_l,
+ * 1 P, 2 R (MK_ERR_ARG on the last level, which has neither). */
+MK_API int mk_amg_level(const mk_amg *F, int32_t level, int32_t which, mk_csr **borrowed);
+/* agg (rows of the level ints; not on the last level) and lmax of a level to the host; either may be NULL. */
+MK_API int mk_amg_download(const mk_amg *F, int32_t level, int32_t *agg_host, double *lmax_host);
+/* The coarse inverse, row major, n_last * n_last doubles.  MK_ERR_STATE when the coarsest level is solved by its smoother. */
+MK_API int mk_amg_coarse(const mk_amg *F, double *inverse_host);
+/* ... and as the preconditioner of the square solvers, exactly like mk_solver_set_precon_cheb. */
+MK_API int mk_solver_set_precon_amg(mk_solver *s, const mk_amg *F);
 /* The least-squares kinds take two preconditioners, applied by the reference as `u = M(Mu)` in the m-space and
  * `v = N(Nv)` in the n-space of the Golub-Kahan process (lls/lsqr.py:189-190,201-202,253-254,265-266 and the same
  * lines of lsmr.py, craig.py, craigmr.py).  Each side holds ONE preconditioner of any of the kinds the square solvers
  * take -- a diagonal, a host callback, a device matrix or composite, an incomplete factorization, an inverse L-BFGS
- * operator, a Chebyshev polynomial preconditioner, an FSAI preconditioner -- and every setter below replaces what its side held (releasing the reference it kept on a matrix or object)
+ * operator, a Chebyshev polynomial preconditioner, an FSAI preconditioner, an AMG preconditioner -- and every setter below replaces what its side held (releasing the reference it kept on a matrix or object)
  * without touching the other side.  MK_ERR_UNSUPPORTED for the six square solvers.  Call before mk_solver_setup.
  *
  * Diagonals: device arrays with the diagonals of M (nrows(A) entries) and N (ncols(A) entries), multiplied inside the
@@ -680,6 +755,7 @@ MK_API int mk_solver_set_lls_precon_callback(mk_solver *s, mk_precon_fn fn_m, vo
  *           square solvers' mk_solver_set_precon_lbfgs, a closed set that tests/test_lbfgs_cpu.py pins name by name.)
  *   _cheb:  a Chebyshev polynomial preconditioner (mk_cheb_create) of a symmetric matrix of that side's size.
  *   _fsai:  an FSAI preconditioner (mk_fsai_create) of a symmetric positive definite matrix of that side's size.
+ *   _amg:   an AMG preconditioner (mk_amg_create) of a symmetric matrix of that side's size.
  * The solver holds a factor or operator until it is destroyed or the side is given something else: destroying the object
  * meanwhile is deferred.  NULL removes what the side holds.  MK_ERR_ARG on a size mismatch or a non-square matrix.
  * Single GPU: with row blocks over several GPUs (mk_csr_set_row_block) only diagonals are supported, mk_solver_setup fails
@@ -690,6 +766,7 @@ MK_API int mk_solver_set_lls_precon_ilu(mk_solver *s, int side, const mk_ilu *F)
 MK_API int mk_solver_set_lls_precon_bfgs(mk_solver *s, int side, const mk_lbfgs *F);
 MK_API int mk_solver_set_lls_precon_cheb(mk_solver *s, int side, const mk_cheb *F);
 MK_API int mk_solver_set_lls_precon_fsai(mk_solver *s, int side, const mk_fsai *F);
+MK_API int mk_solver_set_lls_precon_amg(mk_solver *s, int side, const mk_amg *F);
 /* Everything before the `while` loop of the reference's solve().  rhs_dev has n_local
  * entries; guess_dev may be NULL (x0 = 0).  Neither is modified. */
 MK_API int mk_solver_setup(mk_solver *s, const double *rhs_dev, const double *guess_dev);

@@ -45,6 +45,9 @@ MK_CHEB_MAX_DEGREE = 64   # highest degree of mk_cheb_create
 MK_LANCZOS_INFO_LEN = 5   # entries of mk_csr_lanczos' info
 MK_FSAI_INFO_LEN = 8      # entries of mk_fsai_info
 MK_FSAI_MAX_ROW = 32      # longest pattern row of mk_fsai_create
+MK_AMG_INFO_LEN = 10      # entries of mk_amg_info
+MK_AMG_MAX_LEVELS = 16    # most levels of mk_amg_create
+MK_AMG_MAX_COARSE = 1024  # largest coarse_max of mk_amg_create
 
 MK_ROW_SCALE, MK_ROW_ADD, MK_ROW_SUB, MK_ROW_RSUB, MK_ROWPROG_MAX = 1, 2, 3, 4, 4
 
@@ -173,6 +176,15 @@ PROTOTYPES = {
     "mk_fsai_download": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "mk_fsai_factors": (ctypes.c_int, [c_vp, P(c_vp), P(c_vp)]),
     "mk_solver_set_precon_fsai": (ctypes.c_int, [c_vp, c_vp]),
+    "mk_amg_create": (ctypes.c_int, [c_vp, c_f64, c_i32, c_f64, c_f64, c_i32, c_i32, ctypes.c_uint64, c_i64, P(c_vp)]),
+    "mk_amg_destroy": (ctypes.c_int, [c_vp]),
+    "mk_amg_apply": (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    "mk_amg_info": (ctypes.c_int, [c_vp, c_i32, P(c_i64), c_i32]),
+    "mk_amg_level": (ctypes.c_int, [c_vp, c_i32, c_i32, P(c_vp)]),
+    "mk_amg_download": (ctypes.c_int, [c_vp, c_i32, c_vp, P(c_f64)]),
+    "mk_amg_coarse": (ctypes.c_int, [c_vp, c_vp]),
+    "mk_solver_set_precon_amg": (ctypes.c_int, [c_vp, c_vp]),
+    "mk_solver_set_lls_precon_amg": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp]),
     "mk_csr_lanczos": (ctypes.c_int, [c_vp, c_i32, c_i32, ctypes.c_uint64, c_vp, P(c_f64), P(c_f64), P(c_i64), c_i32]),
     "mk_solver_set_lls_precon_callback": (ctypes.c_int, [c_vp, PRECON_FN, c_vp, PRECON_FN, c_vp]),
     "mk_solver_set_lls_precon": (ctypes.c_int, [c_vp, c_vp, c_vp]),

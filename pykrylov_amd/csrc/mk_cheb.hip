@@ -291,6 +291,8 @@ extern "C" int mk_cheb_create(const mk_csr *A, int32_t degree, double lmin, doub
     return MK_OK;
 }
 
+const MkDeviceOp *mk_cheb_as_op(const mk_cheb *F) { return F; }
+
 extern "C" int mk_cheb_destroy(mk_cheb *F) {
     if (F) F->destroy();                                         // (while solvers still apply it: freed with the last of them)
     return MK_OK;

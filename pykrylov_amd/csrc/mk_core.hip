@@ -1149,53 +1149,86 @@ __global__ __launch_bounds__(MK_BLOCK) void coo_count(int64_t ne, const int32_t 
         atomicAdd(&count[rows[j] + 1], 1);
 }
 
+// an entry's key: its column above its position in the input list (both < 2^31), so that the order of the keys is the
+// order by (column, input position)
 __global__ __launch_bounds__(MK_BLOCK) void coo_scatter(int64_t ne, const int32_t *rows, const int32_t *cols,
-                                                        int32_t *cursor, int32_t *seg_col, int32_t *seg_src) {
+                                                        int32_t *cursor, unsigned long long *seg_key) {
     for (int64_t j = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; j < ne; j += (int64_t)gridDim.x * MK_BLOCK) {
         const int32_t dst = atomicAdd(&cursor[rows[j]], 1);
-        seg_col[dst] = cols[j];
-        seg_src[dst] = (int32_t)j;
+        seg_key[dst] = ((unsigned long long)(uint32_t)cols[j] << 32) | (unsigned long long)j;
     }
 }
 
-// per row: order by (column, input position) -- a total order, so the arbitrary arrival order of the scatter
-// does not matter -- and count the distinct columns
-__global__ __launch_bounds__(MK_BLOCK) void coo_sort_rows(int64_t nrows, const int32_t *start, int32_t *seg_col,
-                                                          int32_t *seg_src, int32_t *ucount) {
+// the keys of one row in ascending order, in place, by one lane: heapsort, for the rows an insertion sort would take
+// quadratic time on (the expanded rows of the sparse products of mk_amg.hip hold thousands of entries)
+__device__ __forceinline__ void coo_heap_sift(unsigned long long *key, int32_t root, int32_t size) {
+    const unsigned long long k = key[root];
+    for (int32_t child = 2 * root + 1; child < size; child = 2 * root + 1) {
+        unsigned long long kc = key[child];
+        if (child + 1 < size) {
+            const unsigned long long k2 = key[child + 1];
+            if (k2 > kc) {
+                kc = k2;
+                ++child;
+            }
+        }
+        if (k >= kc) break;
+        key[root] = kc;
+        root = child;
+    }
+    key[root] = k;
+}
+
+constexpr int32_t MK_COO_INSERTION_MAX = 32;   // longest row the insertion sort takes
+
+// per row: order by (column, input position) -- a total order, so neither the arbitrary arrival order of the scatter nor the
+// sorting method matters -- and count the distinct columns
+__global__ __launch_bounds__(MK_BLOCK) void coo_sort_rows(int64_t nrows, const int32_t *start, unsigned long long *seg_key,
+                                                          int32_t *ucount) {
     for (int64_t r = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * MK_BLOCK) {
         const int32_t lo = start[r], hi = start[r + 1];
-        for (int32_t i = lo + 1; i < hi; ++i) {
-            const int32_t ci = seg_col[i], si = seg_src[i];
-            int32_t j = i - 1;
-            while (j >= lo && (seg_col[j] > ci || (seg_col[j] == ci && seg_src[j] > si))) {
-                seg_col[j + 1] = seg_col[j];
-                seg_src[j + 1] = seg_src[j];
-                --j;
+        if (hi - lo > MK_COO_INSERTION_MAX) {
+            unsigned long long *const key = seg_key + lo;
+            const int32_t size = hi - lo;
+            for (int32_t root = size / 2 - 1; root >= 0; --root) coo_heap_sift(key, root, size);
+            for (int32_t end = size - 1; end > 0; --end) {
+                const unsigned long long top = key[0];
+                key[0] = key[end];
+                key[end] = top;
+                coo_heap_sift(key, 0, end);
             }
-            seg_col[j + 1] = ci;
-            seg_src[j + 1] = si;
+        } else {
+            for (int32_t i = lo + 1; i < hi; ++i) {
+                const unsigned long long ki = seg_key[i];
+                int32_t j = i - 1;
+                while (j >= lo && seg_key[j] > ki) {
+                    seg_key[j + 1] = seg_key[j];
+                    --j;
+                }
+                seg_key[j + 1] = ki;
+            }
         }
         int32_t u = 0;
-        for (int32_t i = lo; i < hi; ++i) u += (i == lo || seg_col[i] != seg_col[i - 1]) ? 1 : 0;
+        for (int32_t i = lo; i < hi; ++i) u += (i == lo || (seg_key[i] >> 32) != (seg_key[i - 1] >> 32)) ? 1 : 0;
         ucount[r + 1] = u;
     }
 }
 
-__global__ __launch_bounds__(MK_BLOCK) void coo_emit(int64_t nrows, const int32_t *start, const int32_t *seg_col,
-                                                     const int32_t *seg_src, const double *vals,
-                                                     const int32_t *indptr, int32_t *indices, double *data) {
+__global__ __launch_bounds__(MK_BLOCK) void coo_emit(int64_t nrows, const int32_t *start, const unsigned long long *seg_key,
+                                                     const double *vals, const int32_t *indptr, int32_t *indices, double *data) {
     for (int64_t r = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; r < nrows; r += (int64_t)gridDim.x * MK_BLOCK) {
         const int32_t lo = start[r], hi = start[r + 1];
         int32_t out = indptr[r] - 1;
         double sum = 0.0;
         for (int32_t i = lo; i < hi; ++i) {
-            if (i == lo || seg_col[i] != seg_col[i - 1]) {
+            const unsigned long long k = seg_key[i];
+            if (i == lo || (k >> 32) != (seg_key[i - 1] >> 32)) {
                 if (i != lo) data[out] = sum;
                 ++out;
-                indices[out] = seg_col[i];
+                indices[out] = (int32_t)(k >> 32);
                 sum = 0.0;
             }
-            sum = sum + vals[seg_src[i]];                   // duplicates: added in input order, starting from 0.0
+            sum = sum + vals[(uint32_t)k];                  // duplicates: added in input order, starting from 0.0
         }
         if (hi > lo) data[out] = sum;
     }
@@ -1204,6 +1237,64 @@ __global__ __launch_bounds__(MK_BLOCK) void coo_emit(int64_t nrows, const int32_
 static inline int mk_grid_for(int64_t n) {
     int64_t g = (n + MK_BLOCK - 1) / MK_BLOCK;
     return (int)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
+}
+
+// The device half: coordinate lists already in device memory (rows in [0, nrows), columns in [0, ncols), nentries < 2^31)
+// and the row starts of the list on the host (start[r + 1] - start[r] = entries of row r, nrows + 1 ints) -> canonical CSR.
+// Scatter by row, per-row sort by (column, list position), emit with the duplicates summed in list order from 0.0.  Also the
+// compress step of the sparse products of mk_amg.hip, whose expanded lists are formed on the device.  Synchronises.
+int mk_coo_compress_device(int64_t nrows, int64_t ncols, int64_t nentries, const int32_t *d_rows, const int32_t *d_cols,
+                           const double *d_vals, const int32_t *start_host, mk_csr **out) {
+    hipStream_t st = mk_ctx().stream;
+    const size_t pb = sizeof(int32_t) * (size_t)(nrows + 1), eb = sizeof(int32_t) * (size_t)(nentries ? nentries : 1);
+    int32_t *d_start = nullptr, *d_cursor = nullptr, *d_ucount = nullptr;
+    unsigned long long *d_key = nullptr;
+    mk_csr *A = nullptr;
+    int rc = MK_OK;
+    auto cleanup = [&]() {
+        hipFree(d_start); hipFree(d_cursor); hipFree(d_key); hipFree(d_ucount);
+    };
+#define MK_TRY(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t _e = (expr);                                                                        \
+        if (_e != hipSuccess) {                                                                        \
+            cleanup();                                                                                 \
+            mk_csr_destroy(A);                                                                         \
+            return mk_fail(MK_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));                 \
+        }                                                                                              \
+    } while (0)
+    MK_TRY(hipMalloc((void **)&d_key, 2 * eb));
+    MK_TRY(hipMalloc((void **)&d_start, pb));
+    MK_TRY(hipMalloc((void **)&d_cursor, pb));
+    MK_TRY(hipMalloc((void **)&d_ucount, pb));
+    MK_TRY(hipMemcpyAsync(d_start, start_host, pb, hipMemcpyHostToDevice, st));
+    MK_TRY(hipMemcpyAsync(d_cursor, start_host, pb, hipMemcpyHostToDevice, st));
+    MK_TRY(hipMemsetAsync(d_ucount, 0, pb, st));
+    if (nentries)
+        hipLaunchKernelGGL(coo_scatter, dim3(mk_grid_for(nentries)), dim3(MK_BLOCK), 0, st, nentries, d_rows, d_cols,
+                           d_cursor, d_key);
+    if (nrows)
+        hipLaunchKernelGGL(coo_sort_rows, dim3(mk_grid_for(nrows)), dim3(MK_BLOCK), 0, st, nrows, d_start, d_key,
+                           d_ucount);
+    std::vector<int32_t> u((size_t)nrows + 1, 0);
+    MK_TRY(hipMemcpyAsync(u.data(), d_ucount, pb, hipMemcpyDeviceToHost, st));
+    MK_TRY(hipStreamSynchronize(st));
+    for (int64_t r = 0; r < nrows; ++r) u[r + 1] += u[r];
+    rc = mk_csr_alloc(nrows, ncols, u[(size_t)nrows], &A);
+    if (rc != MK_OK) {
+        cleanup();
+        return rc;
+    }
+    MK_TRY(hipMemcpyAsync(A->d_indptr, u.data(), pb, hipMemcpyHostToDevice, st));
+    if (nrows)
+        hipLaunchKernelGGL(coo_emit, dim3(mk_grid_for(nrows)), dim3(MK_BLOCK), 0, st, nrows, d_start, d_key,
+                           d_vals, A->d_indptr, A->d_indices, A->d_data);
+    MK_TRY(hipGetLastError());
+    MK_TRY(hipStreamSynchronize(st));
+#undef MK_TRY
+    cleanup();
+    *out = A;
+    return MK_OK;
 }
 
 extern "C" int mk_csr_from_coo(int64_t nrows, int64_t ncols, int64_t nentries, const int32_t *rows,
@@ -1228,66 +1319,32 @@ extern "C" int mk_csr_from_coo(int64_t nrows, int64_t ncols, int64_t nentries, c
         return mk_fail(MK_ERR_UNSUPPORTED, "mk_csr_from_coo: a row with %d entries is too long for the per-row "
                        "device sort; build the CSR arrays on the host (mk_csr_create)", (int)longest);
     hipStream_t st = mk_ctx().stream;
-    const size_t pb = sizeof(int32_t) * (size_t)(nrows + 1), eb = sizeof(int32_t) * (size_t)(nentries ? nentries : 1);
-    int32_t *d_rows = nullptr, *d_cols = nullptr, *d_start = nullptr, *d_cursor = nullptr, *d_scol = nullptr,
-            *d_ssrc = nullptr, *d_ucount = nullptr;
+    const size_t eb = sizeof(int32_t) * (size_t)(nentries ? nentries : 1);
+    int32_t *d_rows = nullptr, *d_cols = nullptr;
     double *d_vals = nullptr;
-    mk_csr *A = nullptr;
-    int rc = MK_OK;
     auto cleanup = [&]() {
-        hipFree(d_rows); hipFree(d_cols); hipFree(d_start); hipFree(d_cursor); hipFree(d_scol); hipFree(d_ssrc);
-        hipFree(d_ucount); hipFree(d_vals);
+        hipFree(d_rows); hipFree(d_cols); hipFree(d_vals);
     };
 #define MK_TRY(expr)                                                                                   \
     do {                                                                                               \
         hipError_t _e = (expr);                                                                        \
         if (_e != hipSuccess) {                                                                        \
             cleanup();                                                                                 \
-            mk_csr_destroy(A);                                                                         \
             return mk_fail(MK_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));                 \
         }                                                                                              \
     } while (0)
     MK_TRY(hipMalloc((void **)&d_rows, eb));
     MK_TRY(hipMalloc((void **)&d_cols, eb));
-    MK_TRY(hipMalloc((void **)&d_scol, eb));
-    MK_TRY(hipMalloc((void **)&d_ssrc, eb));
     MK_TRY(hipMalloc((void **)&d_vals, sizeof(double) * (size_t)(nentries ? nentries : 1)));
-    MK_TRY(hipMalloc((void **)&d_start, pb));
-    MK_TRY(hipMalloc((void **)&d_cursor, pb));
-    MK_TRY(hipMalloc((void **)&d_ucount, pb));
     if (nentries) {
         MK_TRY(hipMemcpyAsync(d_rows, rows, sizeof(int32_t) * (size_t)nentries, hipMemcpyHostToDevice, st));
         MK_TRY(hipMemcpyAsync(d_cols, cols, sizeof(int32_t) * (size_t)nentries, hipMemcpyHostToDevice, st));
         MK_TRY(hipMemcpyAsync(d_vals, vals, sizeof(double) * (size_t)nentries, hipMemcpyHostToDevice, st));
     }
-    MK_TRY(hipMemcpyAsync(d_start, h.data(), pb, hipMemcpyHostToDevice, st));
-    MK_TRY(hipMemcpyAsync(d_cursor, h.data(), pb, hipMemcpyHostToDevice, st));
-    MK_TRY(hipMemsetAsync(d_ucount, 0, pb, st));
-    if (nentries)
-        hipLaunchKernelGGL(coo_scatter, dim3(mk_grid_for(nentries)), dim3(MK_BLOCK), 0, st, nentries, d_rows, d_cols,
-                           d_cursor, d_scol, d_ssrc);
-    if (nrows)
-        hipLaunchKernelGGL(coo_sort_rows, dim3(mk_grid_for(nrows)), dim3(MK_BLOCK), 0, st, nrows, d_start, d_scol,
-                           d_ssrc, d_ucount);
-    std::vector<int32_t> u((size_t)nrows + 1, 0);
-    MK_TRY(hipMemcpyAsync(u.data(), d_ucount, pb, hipMemcpyDeviceToHost, st));
-    MK_TRY(hipStreamSynchronize(st));
-    for (int64_t r = 0; r < nrows; ++r) u[r + 1] += u[r];
-    rc = mk_csr_alloc(nrows, ncols, u[(size_t)nrows], &A);
-    if (rc != MK_OK) {
-        cleanup();
-        return rc;
-    }
-    MK_TRY(hipMemcpyAsync(A->d_indptr, u.data(), pb, hipMemcpyHostToDevice, st));
-    if (nrows)
-        hipLaunchKernelGGL(coo_emit, dim3(mk_grid_for(nrows)), dim3(MK_BLOCK), 0, st, nrows, d_start, d_scol, d_ssrc,
-                           d_vals, A->d_indptr, A->d_indices, A->d_data);
-    MK_TRY(hipGetLastError());
-    MK_TRY(hipStreamSynchronize(st));
 #undef MK_TRY
+    const int rc = mk_coo_compress_device(nrows, ncols, nentries, d_rows, d_cols, d_vals, h.data(), out);
     cleanup();
-    *out = A;
-    return MK_OK;
+    return rc;
 }
 
 // ======================================================================================

@@ -217,6 +217,9 @@ struct mk_csr {
 };
 
 int mk_csr_alloc(int64_t nrows, int64_t ncols, int64_t nnz, mk_csr **out);
+// the device half of mk_csr_from_coo (mk_core.hip): device coordinate lists + the host row starts of the list -> canonical CSR
+int mk_coo_compress_device(int64_t nrows, int64_t ncols, int64_t nentries, const int32_t *d_rows, const int32_t *d_cols,
+                           const double *d_vals, const int32_t *start_host, mk_csr **out);
 void mk_release_operand(const mk_csr *B);   // a borrower lets go: the matrix is destroyed now if its owner already asked for it
 void mk_csr_plan_reset(const mk_csr *A);    // drop the windowed format (it is rebuilt on the next product)
 void mk_csr_march_pref(const mk_csr *A, int pref);   // a solver is being created on A: 1 = CG, 0 = any other loop
@@ -248,12 +251,14 @@ static inline int mk_grid_spmv(int64_t ntiles) {
 
 // k(c) = 0.5 + u(c), u a 53-bit uniform from a splitmix64 hash of the cell number c: the coefficient field of the
 // variable-coefficient generators (mk_core.hip) and, less one, the default start vector of mk_csr_lanczos (mk_lanczos.hip)
-__host__ __device__ static inline double mk_cell_field(int64_t c, uint64_t seed) {
+__host__ __device__ static inline uint64_t mk_cell_hash(int64_t c, uint64_t seed) {
     uint64_t z = ((uint64_t)c + 1ULL) * 0x9E3779B97F4A7C15ULL + seed;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    z = z ^ (z >> 31);
-    return 0.5 + (double)(z >> 11) * 0x1.0p-53;
+    return z ^ (z >> 31);
+}
+__host__ __device__ static inline double mk_cell_field(int64_t c, uint64_t seed) {
+    return 0.5 + (double)(mk_cell_hash(c, seed) >> 11) * 0x1.0p-53;
 }
 
 // Sum over the workgroup, identical value returned to every thread.  Fixed tree:

@@ -31,8 +31,8 @@ int mk_exchange_begin(const mk_csr *A, double *x_ext);     // may leave the mess
 int mk_exchange_wait(const mk_csr *A, hipStream_t stream); // ... until here
 
 // A device object that applies out = P in under the loop's halt words: the incomplete factorizations (mk_ilu.hip), the
-// inverse L-BFGS operator (mk_lbfgs.hip), the Chebyshev polynomial preconditioner (mk_cheb.hip) and the FSAI preconditioner
-// (mk_fsai.hip).  A solver that applies it holds it; destroying it meanwhile is deferred to the
+// inverse L-BFGS operator (mk_lbfgs.hip), the Chebyshev polynomial preconditioner (mk_cheb.hip), the FSAI preconditioner
+// (mk_fsai.hip) and the AMG preconditioner (mk_amg.hip).  A solver that applies it holds it; destroying it meanwhile is deferred to the
 // last release.  The destructor of the derived object frees its device memory.
 struct MkDeviceOp {
     int64_t n = 0;                 // rows
@@ -51,6 +51,9 @@ struct MkDeviceOp {
         else delete this;
     }
 };
+
+// A Chebyshev object as the device operator it is (mk_cheb.hip): the smoother of every level of mk_amg.hip
+const MkDeviceOp *mk_cheb_as_op(const mk_cheb *F);
 
 // A preconditioner slot.  A solver has two (mk_solver::slot): a square solver uses the first, a least-squares solver both,
 // for M (nrows(A) entries) and N (ncols(A) entries).  A diagonal is multiplied inside the loop's kernels (`d`).  With one of

@@ -143,7 +143,7 @@ class HostPrecon(object):
 
 def _device_object_route(precon):
     """The route word of a preconditioner that is a device object of the library, and its plural for messages."""
-    from .tools import ChebyshevPreconditioner, FsaiPreconditioner, IluPreconditioner
+    from .tools import AmgPreconditioner, ChebyshevPreconditioner, FsaiPreconditioner, IluPreconditioner
     from .lbfgs import InverseLBFGSOperator
     if isinstance(precon, IluPreconditioner):                # `tools.ilu0` / `tools.ic0`: triangular sweeps
         return 'ilu', 'incomplete factorizations'
@@ -154,6 +154,8 @@ def _device_object_route(precon):
         return 'cheb', 'Chebyshev preconditioners'
     if isinstance(precon, FsaiPreconditioner):               # `tools.fsai`: two products, G and its transpose
         return 'fsai', 'FSAI preconditioners'
+    if isinstance(precon, AmgPreconditioner):                # `tools.amg`: one V-cycle over its own hierarchy
+        return 'amg', 'AMG preconditioners'
     return None, None
 
 
@@ -167,7 +169,7 @@ def resolve_precon(precon, size, name, owner, partitioned=False):
     * ``'none'``, ``None``;
     * ``'diag'``: an operator that exposes its diagonal (``DiagonalOperator``, linop.py:473-516 -- the docs' Jacobi
       `DiagonalPrec`, examples/bmark.py:14-23) -- the fp64 array, applied INSIDE the kernels;
-    * ``'ilu'`` / ``'lbfgs'`` / ``'cheb'`` / ``'fsai'``: a device object of the library -- itself, applied ON the device by its own
+    * ``'ilu'`` / ``'lbfgs'`` / ``'cheb'`` / ``'fsai'`` / ``'amg'``: a device object of the library -- itself, applied ON the device by its own
       launches;
     * ``'device'``: a CsrOperator, or an operator with a device view (`tools.block_jacobi`, block operators of device
       matrices), square and of that size -- a :class:`DevicePrecon`, a product on the device;

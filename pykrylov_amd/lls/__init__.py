@@ -8,9 +8,9 @@ use); any other operator with ``A * v`` and ``A.T * u`` is called back on the ho
 (:class:`pykrylov_amd.linop.HostOperatorShell`).  Preconditioners `M`, `N` are resolved like the square solvers'
 ``precon``: a diagonal (``DiagonalOperator``, linop.py:473-516; ``mk_solver_set_lls_precon``) acts inside the kernels; a
 device matrix or composite (``tools.block_jacobi``), an incomplete factorization (``tools.ilu0`` / ``tools.ic0``), an
-``InverseLBFGSOperator``, a Chebyshev polynomial preconditioner (``tools.chebyshev``) and an FSAI preconditioner
-(``tools.fsai``) are applied on the device at the
-`u = M(Mu)` / `v = N(Nv)` sites (``mk_solver_set_lls_precon_csr / _ilu / _bfgs / _cheb / _fsai``); any other callable is called back on the host there
+``InverseLBFGSOperator``, a Chebyshev polynomial preconditioner (``tools.chebyshev``), an FSAI preconditioner
+(``tools.fsai``) and an AMG preconditioner (``tools.amg``) are applied on the device at the
+`u = M(Mu)` / `v = N(Nv)` sites (``mk_solver_set_lls_precon_csr / _ilu / _bfgs / _cheb / _fsai / _amg``); any other callable is called back on the host there
 (``mk_solver_set_lls_precon_callback``).  After a solve `solver.precon_route` names the route of each side.  On several GPUs
 the operator is split into row blocks with a replicated column space (:func:`pykrylov_amd.dist.partition_row_blocks`).
 """

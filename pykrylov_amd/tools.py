@@ -651,3 +651,188 @@ class FsaiPreconditioner(LinearOperator):
 
     def __del__(self):
         self.free()
+
+
+def _amg_int(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError('amg: %s must be an integer from %d to %d, got %r' % (name, lo, hi, v))
+    return int(v)
+
+
+def _amg_real(name, v, ok, what):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not ok(float(v)):
+        raise ValueError('amg: %s must be a finite number %s, got %r' % (name, what, v))
+    return float(v)
+
+
+def amg(op, theta=0.0, degree=1, ratio=4.0, omega=4.0 / 3.0, coarse_max=256, max_levels=10, seed=1, expand_cap=0):
+    """Smoothed-aggregation algebraic multigrid of a symmetric device matrix with a positive diagonal (a :class:`CsrOperator`
+    declared ``symmetric=True``) as a DEVICE preconditioner whose apply is one V(1,1)-cycle.  The hierarchy is set up on the
+    GPU: per level the strength graph (`theta`; ``v*v > theta**2 * a_ii * a_jj``), MIS(2) roots from hashed keys (`seed`),
+    aggregates, the prolongator ``P = T - (omega / lmax) D^-1 A T`` with `lmax` the Gershgorin bound of ``D^-1 A``, and the
+    Galerkin product ``P^T (A P)`` as two expand-sort-compress products in row chunks of at most `expand_cap` expanded
+    entries (0: 2**26; the hierarchy does not depend on it).  Coarsening stops at `coarse_max` rows (1 .. 1024), at
+    `max_levels` levels (1 .. 16) or when a level does not shrink; a last level of at most `coarse_max` rows is inverted on
+    the host and applied as a dense matrix, a larger one (or one whose Cholesky factorization breaks down) is solved by its
+    smoother alone.  The smoother of every level is the diagonally scaled Chebyshev polynomial of `degree` on
+    ``[lmax / ratio, lmax]`` (`chebyshev`).  Passed as ``precon=`` to CG / BiCGSTAB / CGS / TFQMR / MINRES / SYMMLQ / GMRES /
+    IDR, or as ``M=`` / ``N=`` to the least-squares solvers, it is applied without a host round trip.  ValueError naming the
+    row for a diagonal entry that is missing, zero or negative (on any level)."""
+    _cheb_operator(op, 'amg', 'the AMG preconditioner')
+    theta = _amg_real('theta', theta, lambda v: v >= 0.0, '>= 0')
+    ratio = _amg_real('ratio', ratio, lambda v: v > 1.0, '> 1')
+    omega = _amg_real('omega', omega, lambda v: v > 0.0, '> 0')
+    degree = _amg_int('degree', degree, 1, _lib.MK_CHEB_MAX_DEGREE)
+    coarse_max = _amg_int('coarse_max', coarse_max, 1, _lib.MK_AMG_MAX_COARSE)
+    max_levels = _amg_int('max_levels', max_levels, 1, _lib.MK_AMG_MAX_LEVELS)
+    seed = _amg_int('seed', seed, 0, 2 ** 64 - 1)
+    expand_cap = _amg_int('expand_cap', expand_cap, 0, 2 ** 31 - 1)
+    return AmgPreconditioner(op, theta, degree, ratio, omega, coarse_max, max_levels, seed, expand_cap)
+
+
+class AmgPreconditioner(LinearOperator):
+    """One V(1,1)-cycle of a smoothed-aggregation hierarchy resident in HBM (`amg`).  ``self * v`` applies it to a NumPy
+    vector, `apply_device` to DeviceArray vectors; solvers given it as ``precon=`` (``M=`` / ``N=``) apply it on the device
+    (mk_solver_set_precon_amg / mk_solver_set_lls_precon_amg).  Attributes: `info` (the totals of mk_amg_info as a dict),
+    `levels` (one dict per level), `operator_complexity`, `grid_complexity`; `level_arrays(l)` downloads a level,
+    `coarse_inverse()` the dense inverse of the last one, `level_handles(l)` gives the borrowed ``mk_csr*`` of a level.
+    `free()` releases this object's reference; a solver that still applies the object keeps it alive."""
+
+    def __init__(self, op, theta, degree, ratio, omega, coarse_max, max_levels, seed, expand_cap):
+        lib = _lib.init()
+        self._lib = lib
+        self._handle = None
+        self._buf = None
+        self._n = int(op.shape[0])
+        self.params = dict(theta=theta, degree=degree, ratio=ratio, omega=omega, coarse_max=coarse_max,
+                           max_levels=max_levels, seed=seed, expand_cap=expand_cap)
+        h = ctypes.c_void_p()
+        rc = lib.mk_amg_create(op.handle, theta, degree, ratio, omega, coarse_max, max_levels, seed, expand_cap, ctypes.byref(h))
+        if rc != 0:
+            msg = lib.mk_last_error().decode(errors='replace')
+            if 'has no positive diagonal entry' in msg:
+                raise ValueError('amg: %s' % msg.split(': ', 1)[-1])
+            _lib.check(rc)
+        self._handle = h.value
+        self._op = op                      # (keeps the matrix's Python owner alive beside the library's own count)
+        LinearOperator.__init__(self, self._n, self._n, matvec=self._apply, symmetric=True, dtype=np.float64)
+
+    handle = property(lambda self: self._live(), doc="Opaque ``mk_amg*`` for libmikrylov.")
+
+    def _info(self, level, names):
+        v = (ctypes.c_int64 * _lib.MK_AMG_INFO_LEN)()
+        _lib.check(self._lib.mk_amg_info(self._live(), level, v, _lib.MK_AMG_INFO_LEN))
+        return dict(zip(names, (int(x) for x in v)))
+
+    @property
+    def info(self):
+        d = self._info(-1, ('levels', 'bytes', 'setup_us', 'launches', 'coarse_dense', 'operator_complexity_x1000',
+                            'grid_complexity_x1000', 'nnz_total', 'rows_total', 'coarse_why'))
+        d['coarse_solver'] = 'inverse' if d['coarse_dense'] else 'smoother'
+        return d
+
+    @property
+    def levels(self):
+        names = ('rows', 'nnz', 'nnz_p', 'aggregates', 'mis_rounds', 'expanded_ap', 'expanded_rap', 'chunks_ap', 'chunks_rap',
+                 'chunks_p')
+        out = []
+        for l in range(self.info['levels']):
+            d = self._info(l, names)
+            lmax = ctypes.c_double()
+            _lib.check(self._lib.mk_amg_download(self._live(), l, None, ctypes.byref(lmax)))
+            d['lmax'] = lmax.value
+            out.append(d)
+        return out
+
+    @property
+    def operator_complexity(self):
+        i = self.info
+        return i['nnz_total'] / float(self._info(0, ('rows', 'nnz'))['nnz'] or 1)
+
+    @property
+    def grid_complexity(self):
+        return self.info['rows_total'] / float(self._n or 1)
+
+    def _live(self):
+        if not self._handle:
+            raise ValueError('the AMG preconditioner has been freed')
+        return self._handle
+
+    def _apply(self, r):
+        h = self._live()
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if self._buf is None:
+            self._buf = _lib.DeviceArray(self._n, zero=False)
+        self._buf.upload(r)
+        _lib.check(self._lib.mk_amg_apply(h, self._buf.ptr, self._buf.ptr))
+        return self._buf.to_numpy()
+
+    def apply_device(self, d_in, d_out):
+        "``d_out`` = one V-cycle on ``d_in``, DeviceArray vectors (`d_in is d_out` allowed); enqueued on the library's stream."
+        for d in (d_in, d_out):
+            if not isinstance(d, _lib.DeviceArray) or d.n != self._n or d.dtype != np.float64 or not d.ptr:
+                raise ValueError('apply_device needs live float64 DeviceArray vectors of %d entries' % self._n)
+        _lib.check(self._lib.mk_amg_apply(self._live(), d_in.ptr, d_out.ptr))
+
+    def level_handles(self, level):
+        """Borrowed ``mk_csr*`` handles ``(A_l, P, R)`` of a level, for ``mk_csr_set_format`` / ``mk_csr_format_info``; P and R
+        are None on the last level.  They belong to this object."""
+        out = []
+        last = level == self.info['levels'] - 1
+        for which in range(3):
+            if which and last:
+                out.append(None)
+                continue
+            h = ctypes.c_void_p()
+            _lib.check(self._lib.mk_amg_level(self._live(), level, which, ctypes.byref(h)))
+            out.append(h.value)
+        return tuple(out)
+
+    def _csr_arrays(self, handle):
+        nr, nc, nnz = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(self._lib.mk_csr_shape(handle, ctypes.byref(nr), ctypes.byref(nc), ctypes.byref(nnz)))
+        indptr = np.empty(nr.value + 1, dtype=np.int32)
+        indices = np.empty(nnz.value, dtype=np.int32)
+        data = np.empty(nnz.value, dtype=np.float64)
+        _lib.check(self._lib.mk_csr_download(handle, indptr.ctypes.data, indices.ctypes.data, data.ctypes.data))
+        return indptr, indices, data, (nr.value, nc.value)
+
+    def level_arrays(self, level):
+        """A level to the host as a dict: ``'A'``, ``'P'``, ``'R'`` as ``(indptr, indices, data, shape)``, ``'agg'`` and
+        ``'lmax'``; P, R and agg are None on the last level."""
+        a, p, r = self.level_handles(level)
+        out = {'A': self._csr_arrays(a), 'P': None, 'R': None, 'agg': None}
+        lmax = ctypes.c_double()
+        if p is not None:
+            out['P'], out['R'] = self._csr_arrays(p), self._csr_arrays(r)
+            agg = np.empty(out['A'][3][0], dtype=np.int32)
+            _lib.check(self._lib.mk_amg_download(self._live(), level, agg.ctypes.data, ctypes.byref(lmax)))
+            out['agg'] = agg
+        else:
+            _lib.check(self._lib.mk_amg_download(self._live(), level, None, ctypes.byref(lmax)))
+        out['lmax'] = lmax.value
+        return out
+
+    def coarse_inverse(self):
+        "The dense inverse of the last level (row major), or None when that level is solved by its smoother alone."
+        if not self.info['coarse_dense']:
+            return None
+        n = self._info(self.info['levels'] - 1, ('rows',))['rows']
+        inv = np.empty((n, n), dtype=np.float64)
+        _lib.check(self._lib.mk_amg_coarse(self._live(), inv.ctypes.data))
+        return inv
+
+    def free(self):
+        if getattr(self, '_buf', None) is not None:
+            self._buf.free()
+            self._buf = None
+        if getattr(self, '_handle', None):
+            try:
+                self._lib.mk_amg_destroy(self._handle)
+            except Exception:
+                pass
+            self._handle = None
+        self._op = None
+
+    def __del__(self):
+        self.free()
