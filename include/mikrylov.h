@@ -371,7 +371,8 @@ typedef enum {
     MK_CRAIG = 9,     /* pykrylov/lls/craig.py:104-520        */
     MK_CRAIGMR = 10,  /* pykrylov/lls/craigmr.py:51-241       */
     MK_GMRES = 11,    /* restarted GMRES(m), right preconditioned (no reference module): a square solver */
-    MK_IDR = 12       /* IDR(s), right preconditioned (no reference module): a square solver */
+    MK_IDR = 12,      /* IDR(s), right preconditioned (no reference module): a square solver */
+    MK_PCG = 13       /* preconditioned CG, the textbook recurrence p = z + beta p (no reference module): a square solver */
 } mk_solver_kind;
 
 #define MK_GMRES_MAX_RESTART 128
@@ -416,6 +417,8 @@ typedef struct {
     double aux[8];            /* MK_GMRES: [0] restarts, [1] steps of the last cycle, [2] bytes of the basis */
                               /* MK_IDR: [0] the s in use (after clamping to n), [1] completed cycles, [2] bytes of P, G and U,
                                * [3] breakdown: 0 none, 1 a zero or non-finite pivot M[k,k], 2 a zero or non-finite om */
+                              /* MK_PCG: [0] the flexible flag in use, [1] breakdown: 0 none, 1 the curvature test <p, A p> > 0 failed
+                               * (`definite` is 0), 2 a <r, M r> that is not positive and finite */
 } mk_result;
 
 typedef struct mk_solver mk_solver;
@@ -439,6 +442,15 @@ MK_API int mk_solver_set_transpose(mk_solver *s, const mk_csr *At);
  * refused there).  Without the call s = 4 and seed = 1.  MK_ERR_UNSUPPORTED on another solver kind.  A pivot or an om that
  * is zero or not finite halts the run (mk_result.aux[3]); x is the last iterate then, as after every step. */
 MK_API int mk_solver_set_idr(mk_solver *s, int32_t shadow_dim, uint64_t seed, const double *shadow);
+/* MK_PCG: preconditioned conjugate gradients for symmetric positive definite A and M, z = M r, p = z + beta p, with every
+ * preconditioner setter of the square solvers; single GPU (MK_ERR_UNSUPPORTED from mk_solver_create for an operator with an
+ * exchange plan or a row block).  mk_params.check_curvature as in MK_CG.  The history holds 2-norms of the recurrence
+ * residual of x.  Without a preconditioner the run is MK_CG's bit for bit.  This setter chooses beta: `flexible` 0 (the
+ * default without the call) beta = <r,z>' / <r,z>; 1 beta = <z', r' - r> / <r,z>, for a preconditioner that is not the same
+ * linear operator at every call (one more inner product per pass).  MK_ERR_ARG unless `flexible` is 0 or 1, MK_ERR_STATE
+ * after mk_solver_setup, MK_ERR_UNSUPPORTED on another solver kind.  mk_solver_vector: 0 = r, 1 = p (after a failed
+ * curvature test: the direction that failed it; x is then untouched by that pass). */
+MK_API int mk_solver_set_pcg(mk_solver *s, int32_t flexible);
 /* Several GPUs: mark `A` as THIS rank's block of consecutive rows of a taller m x n operator (its columns are global
  * and unlocalized; no mk_csr_set_exchange).  The least-squares solvers then keep every m-space vector (rhs, u, r;
  * x of CRAIG-MR) sliced like the rows and every n-space vector (v, w, x) whole on every rank: `A * v` needs no
@@ -458,7 +470,7 @@ MK_API int mk_solver_set_precon_diag(mk_solver *s, const double *diag);
  * its result is formed on the device afterwards.  Not invoked once the loop has halted; in BiCGSTAB / CGS / TFQMR the
  * application that precedes a product happens before that product's loop test, so the callback may run once more
  * than in the reference (its last result is unused; MK_GMRES applies it after the stop test: once per step and once
- * per cycle end; MK_IDR likewise, once per product).  The six square solvers, MK_GMRES and MK_IDR; MK_ERR_UNSUPPORTED for the lls kinds and on partitioned
+ * per cycle end; MK_IDR likewise, once per product).  The six square solvers, MK_GMRES, MK_IDR and MK_PCG (once per pass that does not halt, and once at the set-up of a run that does not end there); MK_ERR_UNSUPPORTED for the lls kinds and on partitioned
  * operators.  Replaces a diagonal set earlier.  Call before mk_solver_setup. */
 typedef int (*mk_precon_fn)(void *user, const double *r_host, double *y_host);
 MK_API int mk_solver_set_precon_callback(mk_solver *s, mk_precon_fn fn, void *user);

@@ -17,6 +17,7 @@ from .cgs import CGS                                                            
 from .tfqmr import TFQMR                                                                        # noqa: F401
 from .gmres import GMRES                                                                        # noqa: F401
 from .idr import IDR                                                                            # noqa: F401
+from .pcg import PCG                                                                            # noqa: F401
 from .minres import Minres                                                                      # noqa: F401
 from .symmlq import Symmlq                                                                      # noqa: F401
 from .lbfgs import InverseLBFGSOperator, LBFGSOperator, CompactLBFGSOperator                    # noqa: F401

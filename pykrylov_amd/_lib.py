@@ -22,6 +22,7 @@ MK_GMRES = 11
 MK_GMRES_MAX_RESTART = 128
 MK_IDR = 12
 MK_IDR_MAX_S = 32
+MK_PCG = 13
 
 
 class MkParams(ctypes.Structure):
@@ -141,6 +142,7 @@ PROTOTYPES = {
     "mk_solver_destroy": (ctypes.c_int, [c_vp]),
     "mk_solver_set_transpose": (ctypes.c_int, [c_vp, c_vp]),
     "mk_solver_set_idr": (ctypes.c_int, [c_vp, c_i32, ctypes.c_uint64, c_vp]),
+    "mk_solver_set_pcg": (ctypes.c_int, [c_vp, c_i32]),
     "mk_csr_set_row_block": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "mk_solver_set_precon_diag": (ctypes.c_int, [c_vp, c_vp]),
     "mk_solver_set_precon_callback": (ctypes.c_int, [c_vp, PRECON_FN, c_vp]),

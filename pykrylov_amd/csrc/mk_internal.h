@@ -192,10 +192,11 @@ struct mk_csr {
     mutable int dependents = 0;
     // brick-march formats (9 / 10) are chosen per matrix but pay only for loops whose product epilogue loads nothing inside
     // the march's pipelined loop (CG, plain products): -1 no solver has asked yet (march allowed), 1 the last solver created
-    // on this matrix was CG, 0 another loop (its products keep the windowed formats 4 / 5); mk_csr_march_pref, mk_format.hip
+    // on this matrix was CG or PCG (CG's product kernels, mk_cg_epi.h), 0 another loop (its products keep the windowed formats
+    // 4 / 5); mk_csr_march_pref, mk_format.hip
     mutable int march_pref = -1;
-    mutable bool no_sym = false;   // the last solver created on the matrix is not CG: a request for format 11 (symmetric march,
-                                   // CG's and plain products' kernels only) is served as format 10
+    mutable bool no_sym = false;   // the last solver created on the matrix is neither CG nor PCG: a request for format 11
+                                   // (symmetric march, CG's and plain products' kernels only) is served as format 10
     mutable int solver_users = 0;  // live solvers on this matrix (the preference only changes while there is none)
     mutable bool doomed = false;
     double *d_comp_tmp = nullptr;  // first product's row sums (sum / difference) or B x (product)
@@ -222,7 +223,7 @@ int mk_coo_compress_device(int64_t nrows, int64_t ncols, int64_t nentries, const
                            const double *d_vals, const int32_t *start_host, mk_csr **out);
 void mk_release_operand(const mk_csr *B);   // a borrower lets go: the matrix is destroyed now if its owner already asked for it
 void mk_csr_plan_reset(const mk_csr *A);    // drop the windowed format (it is rebuilt on the next product)
-void mk_csr_march_pref(const mk_csr *A, int pref);   // a solver is being created on A: 1 = CG, 0 = any other loop
+void mk_csr_march_pref(const mk_csr *A, int pref);   // a solver is being created on A: 1 = CG or PCG, 0 = any other loop
 void mk_csr_count_users(const mk_csr *A, int delta); // a solver was created on / removed from A (and whatever A is composed of)
 
 // grid sizes -------------------------------------------------------------------------

@@ -213,6 +213,7 @@ mk_solver *mk_make_symmlq();
 mk_solver *mk_make_lls(int kind);
 mk_solver *mk_make_gmres();
 mk_solver *mk_make_idr();
+mk_solver *mk_make_pcg();
 
 #ifdef __HIPCC__
 // ------------------------------------------------------------------ small shared kernels

@@ -318,10 +318,17 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
                                "plan or a row block); IDR is single-GPU");
             s = mk_make_idr();
             break;
+        case MK_PCG:
+            if (A->ex.mode >= 0 || A->row_block)
+                return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: the operator is row-partitioned (it carries an exchange "
+                               "plan or a row block); PCG is single-GPU");
+            s = mk_make_pcg();
+            break;
         default: break;
     }
     if (!s) return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: solver kind %d is not available", params->kind);
-    mk_csr_march_pref(A, params->kind == MK_CG ? 1 : 0);     // (before the partial-sum counts are sized for the format in use)
+    // (before the partial-sum counts are sized for the format in use; PCG's product kernels are CG's, mk_cg_epi.h)
+    mk_csr_march_pref(A, params->kind == MK_CG || params->kind == MK_PCG ? 1 : 0);
     int rc = s->init_common(A, params);
     if (rc != MK_OK) {
         delete s;

@@ -227,10 +227,12 @@ class DeviceRun(object):
         # `transpose`: the device operator A.T the least-squares kinds need (mk_solver_set_transpose); their rhs has
         # nrows(A) entries.  `sides`: their M and N, a pair of `resolve_precon` payloads.  `placement_draws`: see _draws().
         # `idr`: (s, seed, shadow) of mk_solver_set_idr, the shadow vectors None or an (s, n) fp64 array.
+        # `pcg`: (flexible,) of mk_solver_set_pcg.
         transpose = params.pop('transpose', None)
         sides = params.pop('sides', None)
         draws = params.pop('placement_draws', None)
         self.idr = params.pop('idr', None)
+        self.pcg = params.pop('pcg', None)
         self._d_shadow = None
         if draws is not None:
             self.placement_draws = int(draws)
@@ -361,6 +363,8 @@ class DeviceRun(object):
         if self.idr is not None:
             _lib.check(lib.mk_solver_set_idr(handle, int(self.idr[0]), int(self.idr[1]),
                                              None if self._d_shadow is None else self._d_shadow.ptr))
+        if self.pcg is not None:
+            _lib.check(lib.mk_solver_set_pcg(handle, int(bool(self.pcg[0]))))
         if self.precon_kind != 'none':
             setter = {'host': 'callback', 'device': 'csr'}.get(self.precon_kind, self.precon_kind)
             user = (None,) if self.precon_kind == 'host' else ()
