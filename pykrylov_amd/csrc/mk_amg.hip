@@ -44,10 +44,10 @@ struct mk_amg : MkDeviceOp {
     int coarse_why = 0;                   // 0 -, 1 the last level is larger than coarse_max, 2 a pivot was not positive
     std::vector<double> h_ainv;           // row major
     double *d_ainv_t = nullptr;           // column major: lanes = rows read consecutive addresses
-    int *d_words = nullptr;               // two zero words: the halt input of a standalone apply
     double setup_us = 0.0;
     size_t bytes = 0;
     ~mk_amg() override;
+    const char *noun() const override { return "AMG preconditioner"; }
     int enqueue(const double *in, double *out, hipStream_t stream, int *flags, int64_t *q) const override;
 };
 
@@ -58,9 +58,8 @@ static inline unsigned amg_grid(int64_t items) {
 #define AMG_ROWS(r, n) for (int64_t r = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; r < (n); r += (int64_t)gridDim.x * MK_BLOCK)
 
 // ------------------------------------------------------------------ set-up kernels
-__global__ void amg_words_init(int *words, unsigned long long *bound, int *status) {
+__global__ void amg_words_init(unsigned long long *bound, int *status) {
     if (threadIdx.x == 0) {
-        if (words) words[0] = words[1] = 0;
         *bound = 0ull;
         status[0] = status[1] = INT_MAX;
     }
@@ -393,16 +392,15 @@ __global__ __launch_bounds__(MK_BLOCK) void amg_dense_kernel(const double *__res
 // solver's kernel counter (halt parity), or null for a standalone run.
 int mk_amg::enqueue(const double *in, double *out, hipStream_t st, int *flags, int64_t *q) const {
     if (n == 0) return MK_OK;
-    int *const fl = q ? flags : d_words;
-    const auto halt = [&] { return q ? MkHalt{flags, (int)((*q)++ & 1), 0} : MkHalt{d_words, 0, 0}; };
+    const auto next = [&] { return halt(flags, q); };
     double *const nopart = nullptr;
     const int L = (int)lev.size();
     const auto smooth = [&](const MkAmgLevel &v, const double *src, double *dst) {
-        return mk_cheb_as_op(v.S)->enqueue(src, dst, st, fl, q);
+        return mk_cheb_as_op(v.S)->enqueue(src, dst, st, flags, q);   // (q null: the smoother's own never-raised words)
     };
     const auto coarse = [&](const MkAmgLevel &v, const double *src, double *dst) {
         if (!coarse_kind) return smooth(v, src, dst);
-        hipLaunchKernelGGL(amg_dense_kernel, dim3(1), dim3(MK_BLOCK), 0, st, d_ainv_t, (int)v.n, src, dst, halt());
+        hipLaunchKernelGGL(amg_dense_kernel, dim3(1), dim3(MK_BLOCK), 0, st, d_ainv_t, (int)v.n, src, dst, next());
         return (int)MK_OK;
     };
     if (L == 1) {
@@ -416,8 +414,8 @@ int mk_amg::enqueue(const double *in, double *out, hipStream_t st, int *flags, i
         const double *b = l ? v.d_b : in;
         int rc = smooth(v, b, v.d_x);
         if (rc != MK_OK) return rc;
-        mk_spmv_launch_blocks(v.A, mk_grid_spmv_for(v.A), st, v.d_x, MkAmgEpi{b, v.d_r, 0}, MkNoGate(), halt, nopart);
-        mk_spmv_launch_blocks(v.R, mk_grid_spmv_for(v.R), st, v.d_r, MkPlainEpi{lev[(size_t)l + 1].d_b}, MkNoGate(), halt, nopart);
+        mk_spmv_launch_blocks(v.A, mk_grid_spmv_for(v.A), st, v.d_x, MkAmgEpi{b, v.d_r, 0}, MkNoGate(), next, nopart);
+        mk_spmv_launch_blocks(v.R, mk_grid_spmv_for(v.R), st, v.d_r, MkPlainEpi{lev[(size_t)l + 1].d_b}, MkNoGate(), next, nopart);
     }
     {
         const MkAmgLevel &v = lev[(size_t)L - 1];
@@ -427,12 +425,12 @@ int mk_amg::enqueue(const double *in, double *out, hipStream_t st, int *flags, i
     for (int l = L - 2; l >= 0; --l) {                           // up: x += P e ; r = b - A x ; x = x + S r
         const MkAmgLevel &v = lev[(size_t)l];
         const double *b = l ? v.d_b : in;
-        mk_spmv_launch_blocks(v.P, mk_grid_spmv_for(v.P), st, lev[(size_t)l + 1].d_x, MkAmgEpi{v.d_x, v.d_x, 1}, MkNoGate(), halt, nopart);
-        mk_spmv_launch_blocks(v.A, mk_grid_spmv_for(v.A), st, v.d_x, MkAmgEpi{b, v.d_r, 0}, MkNoGate(), halt, nopart);
+        mk_spmv_launch_blocks(v.P, mk_grid_spmv_for(v.P), st, lev[(size_t)l + 1].d_x, MkAmgEpi{v.d_x, v.d_x, 1}, MkNoGate(), next, nopart);
+        mk_spmv_launch_blocks(v.A, mk_grid_spmv_for(v.A), st, v.d_x, MkAmgEpi{b, v.d_r, 0}, MkNoGate(), next, nopart);
         const int rc = smooth(v, v.d_r, v.d_r);
         if (rc != MK_OK) return rc;
         hipLaunchKernelGGL(mk_stream_kernel<MkOpAmgAdd>, dim3(mk_grid_stream(v.n)), dim3(MK_BLOCK), 0, st,
-                           MkOpAmgAdd{v.d_x, v.d_r, l ? v.d_x : out}, v.n, halt(), nopart);
+                           MkOpAmgAdd{v.d_x, v.d_r, l ? v.d_x : out}, v.n, next(), nopart);
     }
     MK_HIP(hipGetLastError());
     return mk_ctx().pending_rc;
@@ -455,7 +453,6 @@ mk_amg::~mk_amg() {
         }
     }
     hipFree(d_ainv_t);
-    hipFree(d_words);
 }
 
 // ------------------------------------------------------------------ set-up, host side
@@ -660,11 +657,13 @@ extern "C" int mk_amg_create(const mk_csr *A, double theta, int32_t degree, doub
     };
     unsigned long long *d_bound = nullptr;                       // bits of the Gershgorin bound, then two status words
     AmgScratch top;
-    if (hipMalloc((void **)&F->d_words, 2 * sizeof(int)) != hipSuccess || !top.get(&d_bound, 2)) {
+    if (!top.get(&d_bound, 2)) {
         (void)hipGetLastError();
         return fail(mk_fail(MK_ERR_HIP, "%s: out of device memory", fn));
     }
-    F->bytes += 2 * sizeof(int);
+    const int rc0 = F->init_nohalt(st);
+    if (rc0 != MK_OK) return fail(rc0);
+    F->bytes += 2 * sizeof(int);                                 // (the two halt words)
     int *const d_status = reinterpret_cast<int *>(d_bound + 1);
     F->lev.emplace_back();
     F->lev[0].A = A;
@@ -690,7 +689,7 @@ extern "C" int mk_amg_create(const mk_csr *A, double theta, int32_t degree, doub
         AmgScratch sc;
         double *d_diag = nullptr;
         if (!sc.get(&d_diag, (size_t)n)) return fail(mk_fail(MK_ERR_HIP, "%s: out of device memory on level %d", fn, l));
-        hipLaunchKernelGGL(amg_words_init, dim3(1), dim3(64), 0, st, l ? nullptr : F->d_words, d_bound, d_status);
+        hipLaunchKernelGGL(amg_words_init, dim3(1), dim3(64), 0, st, d_bound, d_status);
         if (n > 0)
             hipLaunchKernelGGL(amg_diag_kernel, dim3((unsigned)(amg_grid(n) < 1024 ? amg_grid(n) : 1024)), dim3(MK_BLOCK), 0, st,
                                Al->d_indptr, Al->d_indices, Al->d_data, n, d_diag, d_bound, d_status);
@@ -851,10 +850,7 @@ extern "C" int mk_amg_destroy(mk_amg *F) {
 }
 
 extern "C" int mk_amg_apply(const mk_amg *F, const double *in_dev, double *out_dev) {
-    MK_REQUIRE_INIT();
-    MK_ARG(F && (F->n == 0 || (in_dev && out_dev)));
-    MK_ARG(MK_ALIGNED16(in_dev) && MK_ALIGNED16(out_dev));
-    return F->enqueue(in_dev, out_dev, mk_ctx().stream, nullptr, nullptr);
+    return MkDeviceOp::apply_standalone(F, in_dev, out_dev);
 }
 
 extern "C" int mk_amg_info(const mk_amg *F, int32_t level, int64_t *info, int32_t cap) {
@@ -922,9 +918,9 @@ extern "C" int mk_amg_coarse(const mk_amg *F, double *inverse_host) {
 }
 
 extern "C" int mk_solver_set_precon_amg(mk_solver *s, const mk_amg *F) {
-    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_amg", "AMG preconditioner");
+    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_amg");
 }
 
 extern "C" int mk_solver_set_lls_precon_amg(mk_solver *s, int side, const mk_amg *F) {
-    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_amg", "AMG preconditioner");
+    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_amg");
 }

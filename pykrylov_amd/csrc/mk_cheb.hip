@@ -34,11 +34,11 @@ struct mk_cheb : MkDeviceOp {
     double *d_res = nullptr;              // residual of the iteration
     double *d_d[2] = {nullptr, nullptr};  // directions d_{j-1}, d_j in turn
     double *d_dinv = nullptr;             // 1 / a_rr (scaled only)
-    int *d_nohalt = nullptr;              // two zero words: the halt input of a standalone apply
     unsigned long long *d_bound = nullptr;   // bits of the Gershgorin bound, then the status word (smallest bad row)
     double setup_us = 0.0;
     size_t bytes = 0;                     // device bytes owned
     ~mk_cheb() override;
+    const char *noun() const override { return "Chebyshev preconditioner"; }
     int enqueue(const double *in, double *out, hipStream_t stream, int *flags, int64_t *q) const override;
 };
 
@@ -154,28 +154,26 @@ __global__ __launch_bounds__(MK_BLOCK) void mk_cheb_bound_kernel(const int32_t *
     if (threadIdx.x == 0) atomicMax(bound, smax);
 }
 
-__global__ void mk_cheb_words_init(unsigned long long *bound, int *status, int *nohalt) {
+__global__ void mk_cheb_words_init(unsigned long long *bound, int *status) {
     if (threadIdx.x == 0) {
         *bound = 0ull;
         *status = INT_MAX;
-        nohalt[0] = 0;
-        nohalt[1] = 0;
     }
 }
 
 // out = p_k(A) in (in == out allowed): one stream launch, then one product launch per step.  `q` = the solver's kernel
-// counter (halt parity), or null for a standalone run (d_nohalt).  Used by mk_cheb_apply and by the solvers'
+// counter (halt parity), or null for a standalone run.  Used by mk_cheb_apply and by the solvers'
 // preconditioner sites (mk_solver.hip, mk_lls.hip).
 int mk_cheb::enqueue(const double *in, double *out, hipStream_t st, int *flags, int64_t *q) const {
     if (n == 0) return MK_OK;
-    const auto halt = [&] { return q ? MkHalt{flags, (int)((*q)++ & 1), 0} : MkHalt{d_nohalt, 0, 0}; };
+    const auto next = [&] { return halt(flags, q); };
     double *const nopart = nullptr;                              // (no fused dots: no partial sums are written)
     hipLaunchKernelGGL(mk_stream_kernel<MkOpChebInit>, dim3(mk_grid_stream(n)), dim3(MK_BLOCK), 0, st,
-                       MkOpChebInit{in, d_dinv, d_res, d_d[0], out, c0}, n, halt(), nopart);
+                       MkOpChebInit{in, d_dinv, d_res, d_d[0], out, c0}, n, next(), nopart);
     const int nt = mk_store_nt(A);
     for (int j = 1; j <= degree; ++j) {
         const MkChebEpi epi{d_d[(j - 1) & 1], d_dinv, d_res, d_d[j & 1], out, c1[j - 1], c2[j - 1], j == degree ? 1 : 0, nt};
-        mk_spmv_launch_blocks(A, mk_grid_spmv_for(A), st, d_d[(j - 1) & 1], epi, MkNoGate(), halt, nopart);
+        mk_spmv_launch_blocks(A, mk_grid_spmv_for(A), st, d_d[(j - 1) & 1], epi, MkNoGate(), next, nopart);
     }
     MK_HIP(hipGetLastError());
     return MK_OK;
@@ -187,7 +185,6 @@ mk_cheb::~mk_cheb() {
     hipFree(d_d[0]);
     hipFree(d_d[1]);
     hipFree(d_dinv);
-    hipFree(d_nohalt);
     hipFree(d_bound);
     if (A) mk_release_operand(A);
 }
@@ -240,14 +237,15 @@ extern "C" int mk_cheb_create(const mk_csr *A, int32_t degree, double lmin, doub
         }
         F->bytes += vbytes;
     }
-    if (hipMalloc((void **)&F->d_nohalt, 2 * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&F->d_bound, 2 * sizeof(unsigned long long)) != hipSuccess) {
+    if (hipMalloc((void **)&F->d_bound, 2 * sizeof(unsigned long long)) != hipSuccess) {
         (void)hipGetLastError();
         return fail(mk_fail(MK_ERR_HIP, "%s: out of device memory", fn));
     }
-    F->bytes += 2 * sizeof(int) + 2 * sizeof(unsigned long long);
+    const int rc = F->init_nohalt(c.stream);
+    if (rc != MK_OK) return fail(rc);
+    F->bytes += 2 * sizeof(int) + 2 * sizeof(unsigned long long);    // (the two halt words; the bound and the status word)
     int *d_status = reinterpret_cast<int *>(F->d_bound + 1);
-    hipLaunchKernelGGL(mk_cheb_words_init, dim3(1), dim3(64), 0, c.stream, F->d_bound, d_status, F->d_nohalt);
+    hipLaunchKernelGGL(mk_cheb_words_init, dim3(1), dim3(64), 0, c.stream, F->d_bound, d_status);
     F->lmax_default = lmax > 0.0 ? 0 : 1;
     F->lmin_default = lmin > 0.0 ? 0 : 1;
     unsigned long long hb[2] = {0ull, 0ull};
@@ -299,10 +297,7 @@ extern "C" int mk_cheb_destroy(mk_cheb *F) {
 }
 
 extern "C" int mk_cheb_apply(const mk_cheb *F, const double *in_dev, double *out_dev) {
-    MK_REQUIRE_INIT();
-    MK_ARG(F && (F->n == 0 || (in_dev && out_dev)));
-    MK_ARG(MK_ALIGNED16(in_dev) && MK_ALIGNED16(out_dev));
-    return F->enqueue(in_dev, out_dev, mk_ctx().stream, nullptr, nullptr);
+    return MkDeviceOp::apply_standalone(F, in_dev, out_dev);
 }
 
 extern "C" int mk_cheb_info(const mk_cheb *F, int64_t *info, int32_t cap) {
@@ -332,9 +327,9 @@ extern "C" int mk_cheb_coefficients(const mk_cheb *F, double *host) {
 }
 
 extern "C" int mk_solver_set_precon_cheb(mk_solver *s, const mk_cheb *F) {
-    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_cheb", "Chebyshev preconditioner");
+    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_cheb");
 }
 
 extern "C" int mk_solver_set_lls_precon_cheb(mk_solver *s, int side, const mk_cheb *F) {
-    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_cheb", "Chebyshev preconditioner");
+    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_cheb");
 }

@@ -27,22 +27,19 @@ constexpr int MK_FSAI_SHORT = 4;          // longest row of the register kernel 
 struct mk_fsai : MkDeviceOp {
     mk_csr *G = nullptr, *Gt = nullptr;   // owned
     double *d_tmp = nullptr;              // G in
-    int *d_words = nullptr;               // two zero words (the halt input of a standalone apply), then the status word
+    int *d_status = nullptr;              // smallest failing row of the set-up (INT_MAX: none)
     int64_t nnz = 0;
     int longest = 0;                      // longest row of G
     double setup_us = 0.0;
     size_t bytes = 0;                     // device bytes owned (CSR arrays, the vector, the words)
     ~mk_fsai() override;
+    const char *noun() const override { return "FSAI preconditioner"; }
     int enqueue(const double *in, double *out, hipStream_t stream, int *flags, int64_t *q) const override;
 };
 
 // ------------------------------------------------------------------ the pattern from A
-__global__ void mk_fsai_words_init(int *words) {
-    if (threadIdx.x == 0) {
-        words[0] = 0;
-        words[1] = 0;
-        words[2] = INT_MAX;
-    }
+__global__ void mk_fsai_status_init(int *status) {
+    if (threadIdx.x == 0) *status = INT_MAX;
 }
 
 // count[r + 1] = stored entries of row r with column <= r; a row that does not end there with its diagonal (or starts with
@@ -231,10 +228,10 @@ static inline int mk_fsai_stride(int mmax) {
 // null for a standalone run.  Used by mk_fsai_apply and by the solvers' preconditioner sites (mk_solver.hip, mk_lls.hip).
 int mk_fsai::enqueue(const double *in, double *out, hipStream_t st, int *flags, int64_t *q) const {
     if (n == 0) return MK_OK;
-    const auto halt = [&] { return q ? MkHalt{flags, (int)((*q)++ & 1), 0} : MkHalt{d_words, 0, 0}; };
+    const auto next = [&] { return halt(flags, q); };
     double *const nopart = nullptr;                              // (no fused dots: no partial sums are written)
-    mk_spmv_launch_blocks(G, mk_grid_spmv_for(G), st, in, MkPlainEpi{d_tmp}, MkNoGate(), halt, nopart);
-    mk_spmv_launch_blocks(Gt, mk_grid_spmv_for(Gt), st, d_tmp, MkPlainEpi{out}, MkNoGate(), halt, nopart);
+    mk_spmv_launch_blocks(G, mk_grid_spmv_for(G), st, in, MkPlainEpi{d_tmp}, MkNoGate(), next, nopart);
+    mk_spmv_launch_blocks(Gt, mk_grid_spmv_for(Gt), st, d_tmp, MkPlainEpi{out}, MkNoGate(), next, nopart);
     MK_HIP(hipGetLastError());
     return MK_OK;
 }
@@ -242,7 +239,7 @@ int mk_fsai::enqueue(const double *in, double *out, hipStream_t st, int *flags, 
 mk_fsai::~mk_fsai() {
     if (mk_ctx().ready) hipStreamSynchronize(mk_ctx().stream);
     hipFree(d_tmp);
-    hipFree(d_words);
+    hipFree(d_status);
     if (G) mk_csr_destroy(G);
     if (Gt) mk_csr_destroy(Gt);
 }
@@ -312,13 +309,15 @@ extern "C" int mk_fsai_create(const mk_csr *A, const int32_t *pat_indptr, const 
     // (16 bytes of slack behind the vector, zeroed: the product kernels read their input in 16-byte pairs)
     const size_t vbytes = sizeof(double) * (size_t)(n > 0 ? n : 1) + 16;
     if (hipMalloc((void **)&F->d_tmp, vbytes) != hipSuccess || hipMemsetAsync(F->d_tmp, 0, vbytes, c.stream) != hipSuccess ||
-        hipMalloc((void **)&F->d_words, 3 * sizeof(int)) != hipSuccess) {
+        hipMalloc((void **)&F->d_status, sizeof(int)) != hipSuccess) {
         (void)hipGetLastError();
         return fail(mk_fail(MK_ERR_HIP, "%s: out of device memory for the vector (%zu bytes)", fn, vbytes));
     }
-    F->bytes += vbytes + 3 * sizeof(int);
-    int *const d_status = F->d_words + 2;
-    hipLaunchKernelGGL(mk_fsai_words_init, dim3(1), dim3(64), 0, c.stream, F->d_words);
+    int rc = F->init_nohalt(c.stream);
+    if (rc != MK_OK) return fail(rc);
+    F->bytes += vbytes + 3 * sizeof(int);                        // (the status word and the two halt words)
+    int *const d_status = F->d_status;
+    hipLaunchKernelGGL(mk_fsai_status_init, dim3(1), dim3(64), 0, c.stream, d_status);
     const size_t pbytes = sizeof(int32_t) * (size_t)(n + 1);
     std::vector<int32_t> h((size_t)n + 1, 0);
     int bad = INT_MAX;
@@ -351,7 +350,7 @@ extern "C" int mk_fsai_create(const mk_csr *A, const int32_t *pat_indptr, const 
     for (int64_t i = 0; i < n; ++i) longest = h[i + 1] - h[i] > longest ? h[i + 1] - h[i] : longest;
     F->longest = longest;
     F->nnz = h[(size_t)n];
-    int rc = mk_csr_alloc(n, n, F->nnz, &F->G);
+    rc = mk_csr_alloc(n, n, F->nnz, &F->G);
     if (rc != MK_OK) return fail(rc);
     mk_csr *G = F->G;
     if (hipMemcpyAsync(G->d_indptr, h.data(), pbytes, hipMemcpyHostToDevice, c.stream) != hipSuccess)
@@ -405,10 +404,7 @@ extern "C" int mk_fsai_destroy(mk_fsai *F) {
 }
 
 extern "C" int mk_fsai_apply(const mk_fsai *F, const double *in_dev, double *out_dev) {
-    MK_REQUIRE_INIT();
-    MK_ARG(F && (F->n == 0 || (in_dev && out_dev)));
-    MK_ARG(MK_ALIGNED16(in_dev) && MK_ALIGNED16(out_dev));
-    return F->enqueue(in_dev, out_dev, mk_ctx().stream, nullptr, nullptr);
+    return MkDeviceOp::apply_standalone(F, in_dev, out_dev);
 }
 
 extern "C" int mk_fsai_info(const mk_fsai *F, int64_t *info, int32_t cap) {
@@ -444,9 +440,9 @@ extern "C" int mk_fsai_factors(const mk_fsai *F, mk_csr **G, mk_csr **Gt) {
 }
 
 extern "C" int mk_solver_set_precon_fsai(mk_solver *s, const mk_fsai *F) {
-    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_fsai", "FSAI preconditioner");
+    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_fsai");
 }
 
 extern "C" int mk_solver_set_lls_precon_fsai(mk_solver *s, int side, const mk_fsai *F) {
-    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_fsai", "FSAI preconditioner");
+    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_fsai");
 }

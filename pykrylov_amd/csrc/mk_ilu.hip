@@ -44,11 +44,11 @@ struct mk_ilu : MkDeviceOp {
     int32_t *d_diag = nullptr;     // position of the diagonal entry of each row
     MkIluSweep fw, bw;
     int fuse = MK_ILU_FUSE_DEFAULT;
-    int *d_nohalt = nullptr;       // two zero words: the halt input of a standalone apply
     int *d_status = nullptr;       // smallest failing row of the factorization (INT_MAX: none)
     double analysis_us = 0.0, factor_us = 0.0;
     size_t bytes = 0;              // device bytes owned by the factor
     ~mk_ilu() override;
+    const char *noun() const override { return "incomplete factorization"; }
     int enqueue(const double *in, double *out, hipStream_t stream, int *flags, int64_t *q) const override;
 };
 
@@ -65,7 +65,7 @@ enum { MK_ILU_FWD = 0, MK_ILU_FWD_DIV = 1, MK_ILU_BWD = 2, MK_ILU_FACT = 3, MK_I
 //   MK_ILU_BWD      out_i = (out_i - sum_{j>i} U_ij out_j) / U_ii           (in place)
 //   MK_ILU_FACT     row i of ILU(0) (IKJ), zero pivots into *status by atomic min
 //   MK_ILU_FACT_IC  row i of IC(0), breakdowns likewise
-// The applies obey the loop's halt words like every kernel of a solver pass (the factorization runs with d_nohalt).
+// The applies obey the loop's halt words like every kernel of a solver pass (the factorization runs with the object's own).
 template <int MODE>
 __global__ __launch_bounds__(MK_BLOCK) void mk_ilu_kernel(MkIluView F, int lev0, int lev1, const double *in, double *out,
                                                          int *status, MkHalt halt) {
@@ -155,27 +155,22 @@ __global__ __launch_bounds__(MK_BLOCK) void mk_ilu_mirror_kernel(double *val, co
     }
 }
 
-__global__ void mk_ilu_status_init(int *status, int *nohalt) {
-    if (threadIdx.x == 0) {
-        *status = INT_MAX;
-        nohalt[0] = 0;
-        nohalt[1] = 0;
-    }
+__global__ void mk_ilu_status_init(int *status) {
+    if (threadIdx.x == 0) *status = INT_MAX;
 }
 
 static MkIluView mk_ilu_view(const mk_ilu *F, const MkIluSweep &S) {
     return MkIluView{F->A->d_indptr, F->A->d_indices, F->d_diag, S.d_rows, S.d_lev, F->d_val};
 }
 
-// every launch of one sweep; `q` = the solver's kernel counter (halt parity), or null for a standalone run (d_nohalt)
+// every launch of one sweep; `q` = the solver's kernel counter (halt parity), or null for a standalone run
 template <int MODE>
 static void mk_ilu_sweep(const mk_ilu *F, const MkIluSweep &S, const double *in, double *out, hipStream_t st, int *flags,
                          int64_t *q) {
     const MkIluView v = mk_ilu_view(F, S);
     for (const MkIluLaunch &l : S.plan) {
-        const MkHalt h = q ? MkHalt{flags, (int)((*q)++ & 1), 0} : MkHalt{F->d_nohalt, 0, 0};
         hipLaunchKernelGGL(mk_ilu_kernel<MODE>, dim3(l.grid), dim3(MK_BLOCK), 0, st, v, l.lev0, l.lev1, in, out,
-                           F->d_status, h);
+                           F->d_status, F->halt(flags, q));
     }
 }
 
@@ -197,7 +192,6 @@ mk_ilu::~mk_ilu() {
     hipFree(fw.d_lev);
     hipFree(bw.d_rows);
     hipFree(bw.d_lev);
-    hipFree(d_nohalt);
     hipFree(d_status);
     if (A) mk_release_operand(A);
 }
@@ -344,16 +338,16 @@ static int mk_ilu_create(const mk_csr *A, int kind, mk_ilu **out) {
         (rc = mk_ilu_upload(&F->bw.d_lev, off_b, &F->bytes)) != MK_OK || (kind && (rc = mk_ilu_upload(&d_tmap, tmap, &tbytes)) != MK_OK))
         return fail(rc);
     const size_t vbytes = sizeof(double) * (size_t)(nnz + MK_CSR_PAD);
-    if (hipMalloc((void **)&F->d_val, vbytes) != hipSuccess || hipMalloc((void **)&F->d_nohalt, 2 * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&F->d_status, sizeof(int)) != hipSuccess)
+    if (hipMalloc((void **)&F->d_val, vbytes) != hipSuccess || hipMalloc((void **)&F->d_status, sizeof(int)) != hipSuccess)
         return fail(mk_fail(MK_ERR_HIP, "%s: out of device memory for the factor", fn));
-    F->bytes += vbytes + 3 * sizeof(int);
+    if ((rc = F->init_nohalt(c.stream)) != MK_OK) return fail(rc);
+    F->bytes += vbytes + 3 * sizeof(int);                        // (the status word and the two halt words)
     const auto t1 = std::chrono::steady_clock::now();
     F->analysis_us = std::chrono::duration<double, std::micro>(t1 - t0).count();
     // factorization: the values of A, then one launch per forward level (or fused run) in level order
     if (hipMemcpyAsync(F->d_val, A->d_data, sizeof(double) * (size_t)(nnz + MK_CSR_PAD), hipMemcpyDeviceToDevice, c.stream) != hipSuccess)
         return fail(mk_fail(MK_ERR_HIP, "%s: copying the matrix values failed", fn));
-    hipLaunchKernelGGL(mk_ilu_status_init, dim3(1), dim3(64), 0, c.stream, F->d_status, F->d_nohalt);
+    hipLaunchKernelGGL(mk_ilu_status_init, dim3(1), dim3(64), 0, c.stream, F->d_status);
     if (kind) mk_ilu_sweep<MK_ILU_FACT_IC>(F, F->fw, nullptr, nullptr, c.stream, nullptr, nullptr);
     else mk_ilu_sweep<MK_ILU_FACT>(F, F->fw, nullptr, nullptr, c.stream, nullptr, nullptr);
     if (kind && nnz > 0) {
@@ -390,18 +384,15 @@ extern "C" int mk_ilu_destroy(mk_ilu *F) {
 }
 
 extern "C" int mk_solver_set_precon_ilu(mk_solver *s, const mk_ilu *F) {
-    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_ilu", "incomplete factorization");
+    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_ilu");
 }
 
 extern "C" int mk_solver_set_lls_precon_ilu(mk_solver *s, int side, const mk_ilu *F) {
-    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_ilu", "incomplete factorization");
+    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_ilu");
 }
 
 extern "C" int mk_ilu_apply(const mk_ilu *F, const double *in_dev, double *out_dev) {
-    MK_REQUIRE_INIT();
-    MK_ARG(F && (F->n == 0 || (in_dev && out_dev)));
-    MK_ARG(MK_ALIGNED16(in_dev) && MK_ALIGNED16(out_dev));
-    return F->enqueue(in_dev, out_dev, mk_ctx().stream, nullptr, nullptr);
+    return MkDeviceOp::apply_standalone(F, in_dev, out_dev);
 }
 
 extern "C" int mk_ilu_info(const mk_ilu *F, int64_t *info, int32_t cap) {

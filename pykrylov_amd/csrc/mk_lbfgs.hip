@@ -30,7 +30,6 @@ struct mk_lbfgs : MkDeviceOp {
     double *d_part = nullptr;                  // MK_LBFGS_SLOTS * MK_MAXP partial sums of its own
     double *d_res = nullptr;                   // totals of a multi-dot (2 npairs + 3)
     double *d_coef = nullptr;                  // coefficients of a combine (2 npairs)
-    int *d_nohalt = nullptr;                   // two zero words: the halt input of a standalone apply
     // host mirror of what `store` decided (store synchronises; it is not inside any loop)
     std::vector<double> ys, yy;                // s_k.y_k, y_k.y_k per slot
     std::vector<double> ss, sy;                // Gram caches by slot, row major: ss[k][l] = s_k.s_l, sy[k][l] = s_k.y_l (k newer than l)
@@ -40,6 +39,7 @@ struct mk_lbfgs : MkDeviceOp {
     size_t bytes = 0;
     mutable int64_t last_launches = 0, applies = 0;
     ~mk_lbfgs() override;
+    const char *noun() const override { return "L-BFGS operator"; }
     int enqueue(const double *in, double *out, hipStream_t stream, int *flags, int64_t *q) const override;
     const double *S(int k) const { return d_S + (size_t)k * (size_t)ld; }
     const double *Y(int k) const { return d_Y + (size_t)k * (size_t)ld; }
@@ -158,10 +158,10 @@ static void mk_lbfgs_launch(const mk_lbfgs *F, int j, int kprev, const double *u
 
 // out = H in by the two-loop recursion (in == out allowed): 2p + 1 launches for p stored pairs; with none a copy, or nothing
 // when in == out.  `q` = the solver's kernel counter (each launch takes the halt word flags[(*q)++ & 1]), or null for a
-// standalone run (d_nohalt).  Used by mk_lbfgs_apply and by the solver's preconditioner sites (mk_solver.hip).
+// standalone run.  Used by mk_lbfgs_apply and by the solver's preconditioner sites (mk_solver.hip).
 int mk_lbfgs::enqueue(const double *in, double *out, hipStream_t st, int *flags, int64_t *q) const {
     const mk_lbfgs *F = this;
-    const auto halt = [&] { return q ? MkHalt{flags, (int)((*q)++ & 1), 0} : MkHalt{F->d_nohalt, 0, 0}; };
+    const auto halt = [&] { return F->halt(flags, q); };
     const int p = F->count;
     F->applies += 1;
     if (p == 0) {
@@ -347,12 +347,10 @@ __global__ __launch_bounds__(MK_BLOCK) void mk_lbfgs_combine_kernel(const double
 }
 
 // ys[k] (NaN marks an empty slot for no reader: the stored slots are 0 .. count-1) and gamma, by one lane
-__global__ void mk_lbfgs_set_kernel(double *sc, int k, double ys, int kg, double gamma, int *nohalt) {
+__global__ void mk_lbfgs_set_kernel(double *sc, int k, double ys, int kg, double gamma) {
     if (threadIdx.x == 0) {
         if (k >= 0) sc[k] = ys;
         sc[kg] = gamma;
-        nohalt[0] = 0;
-        nohalt[1] = 0;
     }
 }
 
@@ -365,7 +363,6 @@ mk_lbfgs::~mk_lbfgs() {
     hipFree(d_part);
     hipFree(d_res);
     hipFree(d_coef);
-    hipFree(d_nohalt);
 }
 
 // ======================================================================================
@@ -393,19 +390,19 @@ extern "C" int mk_lbfgs_create(int64_t n, int32_t npairs, int32_t scaling, mk_lb
     if (hipMalloc((void **)&F->d_S, ring) != hipSuccess || hipMalloc((void **)&F->d_Y, ring) != hipSuccess ||
         hipMalloc((void **)&F->d_sc, nsc) != hipSuccess || hipMalloc((void **)&F->d_part, npart) != hipSuccess ||
         hipMalloc((void **)&F->d_res, nres) != hipSuccess || hipMalloc((void **)&F->d_coef, nres) != hipSuccess ||
-        hipMalloc((void **)&F->d_nohalt, 2 * sizeof(int)) != hipSuccess) {
+        F->init_nohalt(mk_ctx().stream) != MK_OK) {
         (void)hipGetLastError();
         delete F;
         return mk_fail(MK_ERR_HIP, "mk_lbfgs_create: out of device memory for 2 x %d columns of %lld doubles", (int)npairs,
                        (long long)n);
     }
-    F->bytes = 2 * ring + nsc + npart + 2 * nres + 2 * sizeof(int);
+    F->bytes = 2 * ring + nsc + npart + 2 * nres + 2 * sizeof(int);   // (the last term: the two halt words)
     hipStream_t st = mk_ctx().stream;
     MK_HIP(hipMemsetAsync(F->d_S, 0, ring, st));                 // (empty slots download as zeros)
     MK_HIP(hipMemsetAsync(F->d_Y, 0, ring, st));
     MK_HIP(hipMemsetAsync(F->d_sc, 0, nsc, st));
     MK_HIP(hipMemsetAsync(F->d_part, 0, npart, st));
-    hipLaunchKernelGGL(mk_lbfgs_set_kernel, dim3(1), dim3(64), 0, st, F->d_sc, -1, 0.0, 2 * npairs, 1.0, F->d_nohalt);
+    hipLaunchKernelGGL(mk_lbfgs_set_kernel, dim3(1), dim3(64), 0, st, F->d_sc, -1, 0.0, 2 * npairs, 1.0);
     MK_HIP(hipGetLastError());
     *out = F;
     return MK_OK;
@@ -417,11 +414,11 @@ extern "C" int mk_lbfgs_destroy(mk_lbfgs *F) {
 }
 
 extern "C" int mk_solver_set_precon_lbfgs(mk_solver *s, const mk_lbfgs *F) {
-    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_lbfgs", "L-BFGS operator");
+    return mk_set_precon(s, -1, MkPrecon::object(F), "mk_solver_set_precon_lbfgs");
 }
 
 extern "C" int mk_solver_set_lls_precon_bfgs(mk_solver *s, int side, const mk_lbfgs *F) {
-    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_bfgs", "L-BFGS operator");
+    return mk_set_precon(s, side, MkPrecon::object(F), "mk_solver_set_lls_precon_bfgs");
 }
 
 extern "C" int mk_lbfgs_store(mk_lbfgs *F, const double *s_dev, const double *y_dev, double threshold, int32_t *accepted) {
@@ -461,7 +458,7 @@ extern "C" int mk_lbfgs_store(mk_lbfgs *F, const double *s_dev, const double *y_
     if (F->count < np) F->count += 1;
     F->insert = (ins + 1) % np;                                  // lbfgs.py:86-87
     F->gamma = F->scaling ? ys / res[1] : 1.0;                   // lbfgs.py:119 (the newest pair's)
-    hipLaunchKernelGGL(mk_lbfgs_set_kernel, dim3(1), dim3(64), 0, st, F->d_sc, ins, ys, 2 * np, F->gamma, F->d_nohalt);
+    hipLaunchKernelGGL(mk_lbfgs_set_kernel, dim3(1), dim3(64), 0, st, F->d_sc, ins, ys, 2 * np, F->gamma);
     MK_HIP(hipGetLastError());
     MK_HIP(hipStreamSynchronize(st));                            // (the caller may free or overwrite s_dev / y_dev now)
     F->stores += 1;
@@ -480,17 +477,13 @@ extern "C" int mk_lbfgs_restart(mk_lbfgs *F) {
     F->insert = 0;
     F->count = 0;
     F->gamma = 1.0;
-    hipLaunchKernelGGL(mk_lbfgs_set_kernel, dim3(1), dim3(64), 0, mk_ctx().stream, F->d_sc, -1, 0.0, 2 * F->npairs, 1.0,
-                       F->d_nohalt);
+    hipLaunchKernelGGL(mk_lbfgs_set_kernel, dim3(1), dim3(64), 0, mk_ctx().stream, F->d_sc, -1, 0.0, 2 * F->npairs, 1.0);
     MK_HIP(hipGetLastError());
     return MK_OK;
 }
 
 extern "C" int mk_lbfgs_apply(const mk_lbfgs *F, const double *in_dev, double *out_dev) {
-    MK_REQUIRE_INIT();
-    MK_ARG(F && in_dev && out_dev);
-    MK_ARG(MK_ALIGNED16(in_dev) && MK_ALIGNED16(out_dev));
-    return F->enqueue(in_dev, out_dev, mk_ctx().stream, nullptr, nullptr);
+    return MkDeviceOp::apply_standalone(F, in_dev, out_dev);
 }
 
 extern "C" int mk_lbfgs_forward_dots(const mk_lbfgs *F, const double *in_dev, int32_t use_gamma, double *a_host) {

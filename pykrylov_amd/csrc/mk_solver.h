@@ -30,18 +30,29 @@ int mk_comm_allgather(const double *mine_dev, double *full_dev, int64_t count_pe
 int mk_exchange_begin(const mk_csr *A, double *x_ext);     // may leave the messages in flight on a second stream
 int mk_exchange_wait(const mk_csr *A, hipStream_t stream); // ... until here
 
-// A device object that applies out = P in under the loop's halt words: the incomplete factorizations (mk_ilu.hip), the
-// inverse L-BFGS operator (mk_lbfgs.hip), the Chebyshev polynomial preconditioner (mk_cheb.hip), the FSAI preconditioner
-// (mk_fsai.hip) and the AMG preconditioner (mk_amg.hip).  A solver that applies it holds it; destroying it meanwhile is deferred to the
-// last release.  The destructor of the derived object frees its device memory.
+// A device object that applies out = P in by launches of its own, inside a solver's loop under the loop's halt words or
+// standalone.  What every kind shares is here: the row count, the count of its holders (a solver that applies the object holds
+// it; destroying it meanwhile is deferred to the last release), the two never-raised halt words of a launch outside a loop,
+// and the standalone apply behind mk_<kind>_apply.  A kind derives from it, gives `enqueue` and `noun`, calls `init_nohalt`
+// in its create path before its first launch, and frees its own device memory in its destructor (after draining the stream;
+// the base destructor then frees the words).
 struct MkDeviceOp {
     int64_t n = 0;                 // rows
     mutable int users = 0;         // solvers holding the object
     mutable bool doomed = false;   // `destroy` was called while solvers still held it
-    virtual ~MkDeviceOp() = default;
-    // out = P in on `stream` (in == out allowed); every launch takes the halt word flags[(*q)++ & 1] (q null: a standalone
-    // run, never halted)
+    int *d_nohalt = nullptr;       // two zero words (owned): the halt input of a launch that no loop can halt
+    virtual ~MkDeviceOp() { hipFree(d_nohalt); }
+    // what the object is, for the messages of the setters: "the <noun> has ... rows"
+    virtual const char *noun() const = 0;
+    // out = P in on `stream` (in == out allowed); every launch takes `halt(flags, q)`
     virtual int enqueue(const double *in, double *out, hipStream_t stream, int *flags, int64_t *q) const = 0;
+    // allocates the two words and zeroes them in stream order
+    int init_nohalt(hipStream_t stream);
+    // the halt words of the next launch: flags[(*q)++ & 1] of the loop whose kernel counter is `q`, or, q null (a standalone
+    // run, the object's own set-up), the words that are never raised
+    MkHalt halt(int *flags, int64_t *q) const { return q ? MkHalt{flags, (int)((*q)++ & 1), 0} : MkHalt{d_nohalt, 0, 0}; }
+    // mk_<kind>_apply: the argument checks of a device vector that crosses the C ABI, then `enqueue` on the context's stream
+    static int apply_standalone(const MkDeviceOp *F, const double *in_dev, double *out_dev);
     void hold() const { users += 1; }
     void release() const {
         if (--users <= 0 && doomed) delete this;
@@ -67,8 +78,8 @@ enum MkPreconKind {
                            // pinned buffers
     MK_PRECON_CSR,         // mk_solver_set_precon_csr / _lls_precon_csr: a device matrix or composite `op` (counted in
                            // op->dependents), e.g. the inverted diagonal blocks of block-Jacobi; the product stays in HBM
-    MK_PRECON_OBJECT       // mk_solver_set_precon_ilu / _lbfgs / _cheb / _fsai, mk_solver_set_lls_precon_ilu / _bfgs / _cheb / _fsai: a held
-                           // MkDeviceOp `obj`
+    MK_PRECON_OBJECT       // the setter pair of a device object's kind, which lives with the kind: a held MkDeviceOp `obj`,
+                           // applied by `obj->enqueue` with the loop's halt words and kernel counter
 };
 
 struct MkPrecon {
@@ -124,9 +135,9 @@ struct mk_solver {
     const double *d_prec() const { return slot[0].d; }
     bool general_precon() const { return slot[0].general(); }
     // `next` replaces whatever `into` (one of `slot`) holds; MK_PRECON_NONE leaves it empty.  The messages name the entry
-    // point `who`, the slot (`name`: "the preconditioner", "M", "N") and, for an object, what it is (`noun`).  The one place
-    // that validates a replacement, gives a slot its ones and the solver its pinned buffers, and moves a reference.
-    int attach(MkPrecon &into, const MkPrecon &next, const char *who, const char *name, const char *noun);
+    // point `who`, the slot (`name`: "the preconditioner", "M", "N") and, for an object, what it is (its `noun`).  The one
+    // place that validates a replacement, gives a slot its ones and the solver its pinned buffers, and moves a reference.
+    int attach(MkPrecon &into, const MkPrecon &next, const char *who, const char *name);
     int apply_precon(const double *in_dev, double *out_dev, bool force = false) {   // out = precon * in ; unless `force`, a no-op once the loop has halted
         return apply_slot(slot[0], in_dev, out_dev, force);
     }
@@ -202,7 +213,7 @@ struct mk_solver {
 
 // Where every extern "C" setter ends: `next` into the slot of a square solver (`side` < 0; refused if the solver kind has no
 // hook) or into side M / N of a least-squares solver (refused on any other); then mk_solver::attach
-int mk_set_precon(mk_solver *s, int side, const MkPrecon &next, const char *who, const char *noun = nullptr);
+int mk_set_precon(mk_solver *s, int side, const MkPrecon &next, const char *who);
 
 mk_solver *mk_make_cg();
 mk_solver *mk_make_bicgstab();

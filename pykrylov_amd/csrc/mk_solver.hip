@@ -365,7 +365,25 @@ __global__ __launch_bounds__(MK_BLOCK) void mk_fill_kernel(double *v, int64_t n,
     for (int64_t i = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * MK_BLOCK) v[i] = a;
 }
 
-int mk_solver::attach(MkPrecon &into, const MkPrecon &next, const char *who, const char *name, const char *noun) {
+// ------------------------------------------------------------------ device objects (MkDeviceOp, mk_solver.h)
+int MkDeviceOp::init_nohalt(hipStream_t stream) {
+    if (hipMalloc((void **)&d_nohalt, 2 * sizeof(int)) != hipSuccess || hipMemsetAsync(d_nohalt, 0, 2 * sizeof(int), stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return mk_fail(MK_ERR_HIP, "out of device memory for the halt words of a device object");
+    }
+    return MK_OK;
+}
+
+// (an L-BFGS operator has n >= 1, so that `n == 0 ||` asks of it what mk_lbfgs_apply always asked: both pointers)
+int MkDeviceOp::apply_standalone(const MkDeviceOp *F, const double *in_dev, double *out_dev) {
+    MK_REQUIRE_INIT();
+    MK_ARG(F && (F->n == 0 || (in_dev && out_dev)));
+    MK_ARG(MK_ALIGNED16(in_dev) && MK_ALIGNED16(out_dev));
+    return F->enqueue(in_dev, out_dev, mk_ctx().stream, nullptr, nullptr);
+}
+
+int mk_solver::attach(MkPrecon &into, const MkPrecon &next, const char *who, const char *name) {
+    const char *noun = next.kind == MK_PRECON_OBJECT ? next.obj->noun() : "";
     // what the kind asks of the solver's operator (only a diagonal or a device matrix may be rank local) and of its own size
     if (next.kind == MK_PRECON_HOST && A->ex.mode >= 0)
         return mk_fail(MK_ERR_UNSUPPORTED, "%s: host preconditioner callbacks are single-GPU (the vector would have to be "
@@ -406,22 +424,21 @@ int mk_solver::attach(MkPrecon &into, const MkPrecon &next, const char *who, con
     return MK_OK;
 }
 
-int mk_set_precon(mk_solver *s, int side, const MkPrecon &next, const char *who, const char *noun) {
+int mk_set_precon(mk_solver *s, int side, const MkPrecon &next, const char *who) {
     MK_ARG(s);
     if (side < 0) {
         if (!s->takes_precon())                              // (its slot is empty and stays so: nothing to remove)
             return next.kind == MK_PRECON_NONE ? (int)MK_OK
                                                : mk_fail(MK_ERR_UNSUPPORTED, "%s: this solver kind has no preconditioner hook", who);
-        return s->attach(s->slot[0], next, who, "the preconditioner", noun);
+        return s->attach(s->slot[0], next, who, "the preconditioner");
     }
     MK_ARG(side == MK_LLS_SIDE_M || side == MK_LLS_SIDE_N);
     if (!mk_is_lls(s)) return mk_fail(MK_ERR_UNSUPPORTED, "%s: not a least-squares solver", who);
-    return s->attach(s->slot[side], next, who, side == MK_LLS_SIDE_N ? "N" : "M", noun);
+    return s->attach(s->slot[side], next, who, side == MK_LLS_SIDE_N ? "N" : "M");
 }
 
-// Every setter REPLACES whatever its slot held; a NULL argument leaves the slot empty.  (The setters of the device objects,
-// mk_solver_set_precon_ilu / _lbfgs / _cheb and mk_solver_set_lls_precon_ilu / _bfgs / _cheb, live with their types in
-// mk_ilu.hip / mk_lbfgs.hip / mk_cheb.hip.)
+// Every setter REPLACES whatever its slot held; a NULL argument leaves the slot empty.  (The two setters of a kind of device
+// object live with its type.)
 extern "C" int mk_solver_set_precon_diag(mk_solver *s, const double *diag) {
     MK_ARG(MK_ALIGNED16(diag));
     return mk_set_precon(s, -1, MkPrecon::diagonal(diag), "mk_solver_set_precon_diag");

@@ -141,22 +141,33 @@ class HostPrecon(object):
         return _lib.PRECON_FN(call)
 
 
+# Route word of `resolve_precon` -> the suffixes of the C setters ``mk_solver_set_precon_<square>`` and
+# ``mk_solver_set_lls_precon_<lls>`` that attach it (include/mikrylov.h).  The two-sided setters of a diagonal and of a
+# callback take M and N in one call: `DeviceRun._apply_precon`.
+PRECON_SETTERS = {
+    'diag': ('diag', ''),
+    'host': ('callback', 'callback'),
+    'device': ('csr', 'csr'),
+    'ilu': ('ilu', 'ilu'),
+    'lbfgs': ('lbfgs', 'bfgs'),
+    'cheb': ('cheb', 'cheb'),
+    'fsai': ('fsai', 'fsai'),
+    'amg': ('amg', 'amg'),
+}
+
+
+def precon_setter(route, lls=False):
+    "The name of the C setter of a route word, of a square or of a least-squares solver."
+    suffix = PRECON_SETTERS[route][int(lls)]
+    return ('mk_solver_set_lls_precon' if lls else 'mk_solver_set_precon') + ('_' + suffix if suffix else '')
+
+
 def _device_object_route(precon):
-    """The route word of a preconditioner that is a device object of the library, and its plural for messages."""
-    from .tools import AmgPreconditioner, ChebyshevPreconditioner, FsaiPreconditioner, IluPreconditioner
-    from .lbfgs import InverseLBFGSOperator
-    if isinstance(precon, IluPreconditioner):                # `tools.ilu0` / `tools.ic0`: triangular sweeps
-        return 'ilu', 'incomplete factorizations'
-    # (the forward L-BFGS classes are not preconditioners and stay on the host-callback route)
-    if isinstance(precon, InverseLBFGSOperator) and precon._is_inverse:    # the two-loop recursion
-        return 'lbfgs', 'L-BFGS operators'
-    if isinstance(precon, ChebyshevPreconditioner):          # `tools.chebyshev`: one product of its matrix per step
-        return 'cheb', 'Chebyshev preconditioners'
-    if isinstance(precon, FsaiPreconditioner):               # `tools.fsai`: two products, G and its transpose
-        return 'fsai', 'FSAI preconditioners'
-    if isinstance(precon, AmgPreconditioner):                # `tools.amg`: one V-cycle over its own hierarchy
-        return 'amg', 'AMG preconditioners'
-    return None, None
+    """The route word of a preconditioner that is a device object of the library, and its plural for messages: what its
+    class says (`tools.DevicePreconditioner`, `lbfgs.InverseLBFGSOperator`; None on the forward L-BFGS classes, which are
+    not preconditioners and stay on the host-callback route)."""
+    cls = type(precon)
+    return getattr(cls, 'route', None), getattr(cls, 'plural', None)
 
 
 def resolve_precon(precon, size, name, owner, partitioned=False):
@@ -279,8 +290,9 @@ class DeviceRun(object):
         C setter of the kind takes."""
         if precon is None:
             return 'none', None, None
-        if _device_object_route(precon)[0] is not None:
-            return _device_object_route(precon)[0], precon, precon._live
+        route = _device_object_route(precon)[0]
+        if route is not None:
+            return route, precon, precon._live
         if isinstance(precon, DevicePrecon):
             return 'device', precon, lambda: precon.dev.handle
         if isinstance(precon, HostPrecon):
@@ -366,9 +378,8 @@ class DeviceRun(object):
         if self.pcg is not None:
             _lib.check(lib.mk_solver_set_pcg(handle, int(bool(self.pcg[0]))))
         if self.precon_kind != 'none':
-            setter = {'host': 'callback', 'device': 'csr'}.get(self.precon_kind, self.precon_kind)
             user = (None,) if self.precon_kind == 'host' else ()
-            _lib.check(getattr(lib, 'mk_solver_set_precon_' + setter)(handle, self._precon_arg(), *user))
+            _lib.check(getattr(lib, precon_setter(self.precon_kind))(handle, self._precon_arg(), *user))
         if self.sides is None:
             return
         # M and N: the callbacks, then the diagonals (a NULL side of these two setters leaves another kind alone), then
@@ -376,13 +387,13 @@ class DeviceRun(object):
         kinds = [kind for kind, _, _ in self.sides]
         if 'host' in kinds:
             fns = [arg() if kind == 'host' else ctypes.cast(None, _lib.PRECON_FN) for kind, _, arg in self.sides]
-            _lib.check(lib.mk_solver_set_lls_precon_callback(handle, fns[0], None, fns[1], None))
+            _lib.check(getattr(lib, precon_setter('host', lls=True))(handle, fns[0], None, fns[1], None))
         if 'diag' in kinds:
-            _lib.check(lib.mk_solver_set_lls_precon(handle, *[arg() if kind == 'diag' else None for kind, _, arg in self.sides]))
+            diags = [arg() if kind == 'diag' else None for kind, _, arg in self.sides]
+            _lib.check(getattr(lib, precon_setter('diag', lls=True))(handle, *diags))
         for side, (kind, _, arg) in enumerate(self.sides):
             if kind not in ('none', 'host', 'diag'):
-                setter = {'device': 'csr', 'lbfgs': 'bfgs'}.get(kind, kind)
-                _lib.check(getattr(lib, 'mk_solver_set_lls_precon_' + setter)(handle, side, arg()))
+                _lib.check(getattr(lib, precon_setter(kind, lls=True))(handle, side, arg()))
 
     def _timed_passes(self, handle, warm=4, passes=12):
         g = None if self.d_guess is None else self.d_guess.ptr

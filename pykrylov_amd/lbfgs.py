@@ -30,7 +30,7 @@ class InverseLBFGSOperator(LinearOperator):
     `free()`, and `store` takes :class:`pykrylov_amd._lib.DeviceArray` arguments without a host copy.  The device object
     is created on first use, so argument errors are raised without a GPU."""
 
-    _is_inverse = True      # what KrylovMethod._device_precon hands to the device loop
+    route, plural = 'lbfgs', 'L-BFGS operators'     # (generic.resolve_precon: the device loop applies the two-loop recursion)
     _use_gamma = True
 
     def __init__(self, n, npairs=5, **kwargs):
@@ -205,7 +205,7 @@ class CompactLBFGSOperator(InverseLBFGSOperator):
     `InverseLBFGSOperator`, with `scaling` on or off.  Per product: one multi-dot pass over the 2p stored columns, a
     2p x 2p solve on the host, one combined update."""
 
-    _is_inverse = False
+    route = None            # no preconditioner: a solver given it calls it back on the host
 
     def _minimat(self, p, gamma):
         """The reference's small matrix (lbfgs.py:228-243) from the Gram entries cached when each pair was stored."""

@@ -138,108 +138,110 @@ def block_jacobi(op, block_size):
     return CsrOperator(ip, c, v, (n, n), symmetric=bool(getattr(op, 'symmetric', False)))
 
 
-def _ilu_operator(op, what, symmetric=False):
-    """Shape / kind checks shared by `ilu0` and `ic0`, made before the device is touched."""
+def _device_matrix(op, what, noun, symmetric=True, factor=False):
+    """Kind / shape checks of the matrix a device object is made from (`ilu0`, `ic0`, `chebyshev`, `lanczos`, `fsai`,
+    `amg`), made before the device is touched; `noun` names what is single-GPU.  The order of the two groups is each
+    caller's own and stays as it was: a row-partitioned operator is not square (its columns are [own | received]), so
+    `ilu0` / `ic0` (`factor`) say ValueError "square" of it and the others NotImplementedError "row-partitioned";
+    tests/test_ilu_cpu.py pins the first order on an object that is no CsrOperator either."""
     shape = getattr(op, 'shape', None)
     if shape is None or len(shape) != 2:
         raise TypeError('%s needs an operator with a `.shape`; got %r' % (what, type(op).__name__))
-    if shape[0] != shape[1]:
-        raise ValueError('%s needs a square operator, got shape %s' % (what, (shape,)))
-    if symmetric and not getattr(op, 'symmetric', False):
-        raise ValueError('%s needs a symmetric operator (declared with symmetric=True)' % what)
-    if getattr(op, 'local_size', None) is not None:
-        raise NotImplementedError('%s: the operator is row-partitioned; the incomplete factorizations are single-GPU '
-                                  '(rank-local factors are not available)' % what)
-    from .linop import CsrOperator
-    if not isinstance(op, CsrOperator):
-        raise TypeError('%s: %r holds no CSR arrays on the device; form its matrix (e.g. `to_csr_arrays()` of a device '
-                        'operator) and wrap it in a CsrOperator to factor it' % (what, type(op).__name__))
+
+    def shaped():
+        if shape[0] != shape[1]:
+            raise ValueError('%s needs a square operator, got shape %s' % (what, (shape,)))
+        if symmetric and not getattr(op, 'symmetric', False):
+            raise ValueError('%s needs a symmetric operator (declared with symmetric=True)' % what)
+
+    def placed():
+        from .linop import CsrOperator
+        if getattr(op, 'local_size', None) is not None:
+            raise NotImplementedError('%s: the operator is row-partitioned; %s%s single-GPU%s' % (
+                what, noun, ' are' if factor else ' is', ' (rank-local factors are not available)' if factor else ''))
+        if not isinstance(op, CsrOperator):
+            raise TypeError('%s: %r holds no CSR arrays on the device; form its matrix (e.g. `to_csr_arrays()` of a device '
+                            'operator) and wrap it in a CsrOperator%s' % (what, type(op).__name__,
+                                                                         ' to factor it' if factor else ''))
+    for check in ((shaped, placed) if factor else (placed, shaped)):
+        check()
     return op
 
 
-def ilu0(op):
-    """ILU(0) of a square device matrix (a :class:`CsrOperator`) as a DEVICE preconditioner: the factor is computed on the
-    GPU on the pattern of `op` (every row must store its diagonal), and ``precon * r`` -- inside a solver's loop or on a
-    NumPy vector -- is the pair of level-scheduled triangular solves ``U^-1 L^-1 r`` (mk_ilu_apply).  Passed as
-    ``precon=`` to CG / BiCGSTAB / CGS / TFQMR / MINRES / SYMMLQ it is applied at the reference's preconditioner sites
-    without a host round trip.  Raises MkError on a zero pivot (naming the row)."""
-    _ilu_operator(op, 'ilu0')
-    return IluPreconditioner(op, 0)
+def _checked_int(what, name, v, lo, hi, must=None):
+    """`v` as an int if it is an integer (no bool) from `lo` to `hi`; ValueError naming `what` and `name` otherwise."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError('%s: %s must be %s, got %r' % (what, name, must or 'an integer from %d to %d' % (lo, hi), v))
+    return int(v)
 
 
-def ic0(op):
-    """IC(0) (incomplete Cholesky, no fill) of a symmetric device matrix: ``M = L L^T`` on the lower pattern of `op`, as a
-    symmetric device preconditioner like :func:`ilu0` (MINRES' symmetry check of the preconditioner passes).  Raises
-    ValueError for an operator not declared symmetric, MkError for a pattern that is not symmetric or a pivot that is not
-    positive (naming the row)."""
-    _ilu_operator(op, 'ic0', symmetric=True)
-    return IluPreconditioner(op, 1)
+class DevicePreconditioner(LinearOperator):
+    """What the device preconditioner objects of this module share: a handle of libmikrylov.so whose entry points are
+    ``mk_<_abi>_apply`` / ``_info`` / ``_destroy``.  ``self * v`` applies the object to a NumPy vector,
+    `apply_device` to DeviceArray vectors; a solver given it as ``precon=`` (``M=`` / ``N=``) applies it on the device
+    (``mk_solver_set_precon_<route>``, `generic.PRECON_SETTERS`).  `free()` releases this object's reference; a solver
+    that still applies the object keeps it alive.  A kind gives the class attributes below, creates its handle and ends
+    its constructor with `_attach`."""
 
+    route = None            # the word of `generic.resolve_precon`
+    plural = None           # '... are single-GPU'
+    _noun = None            # '... has been freed'
+    _abi = None             # the stem of mk_<stem>_apply / _info / _destroy
+    _info_names = ()
+    _handle = _buf = _op = None
 
-class IluPreconditioner(LinearOperator):
-    """M^-1 of an ILU(0) / IC(0) factor resident in HBM (`ilu0`, `ic0`).  ``self * v`` applies it to a NumPy vector;
-    solvers given it as ``precon=`` apply it on the device (mk_solver_set_precon_ilu).  Attributes: `kind`
-    ('ilu0' / 'ic0'), `levels` and `launches` (forward, backward sweep), `info` (mk_ilu_info as a dict).
-    `free()` releases this object's reference; a solver that still applies the factor keeps it alive."""
-
-    def __init__(self, op, kind):
-        lib = _lib.init()
-        h = ctypes.c_void_p()
-        fn = lib.mk_ic0_create if kind else lib.mk_ilu0_create
-        _lib.check(fn(op.handle, ctypes.byref(h)))
-        self._lib = lib
-        self._handle = h.value
-        self._n = int(op.shape[0])
-        self._nnz = int(op.nnz)
-        self._op = op                      # (its pattern: factor_arrays() pairs it with the values)
-        self.kind = 'ic0' if kind else 'ilu0'
-        self._buf = None
-        LinearOperator.__init__(self, self._n, self._n, matvec=self._apply, symmetric=bool(kind), dtype=np.float64)
-
-    handle = property(lambda self: self._handle, doc="Opaque ``mk_ilu*`` for libmikrylov.")
-
-    @property
-    def info(self):
-        names = ('kind', 'rows', 'nnz', 'levels_forward', 'levels_backward', 'launches_forward', 'launches_backward',
-                 'widest_level', 'bytes', 'fuse_rows', 'analysis_us', 'factor_us')
-        v = (ctypes.c_int64 * _lib.MK_ILU_INFO_LEN)()
-        _lib.check(self._lib.mk_ilu_info(self._live(), v, _lib.MK_ILU_INFO_LEN))
-        return dict(zip(names, (int(x) for x in v)))
-
-    levels = property(lambda self: (self.info['levels_forward'], self.info['levels_backward']))
-    launches = property(lambda self: (self.info['launches_forward'], self.info['launches_backward']))
+    def _attach(self, handle, n, symmetric, op=None):
+        """`op`: the matrix the object was made from, where its Python owner has to stay alive beside the library's count."""
+        self._lib = _lib.init()
+        self._handle, self._n, self._op = handle, int(n), op
+        LinearOperator.__init__(self, self._n, self._n, matvec=self._apply, symmetric=symmetric, dtype=np.float64)
 
     def _live(self):
         if not self._handle:
-            raise ValueError('the factor has been freed')
+            raise ValueError('%s has been freed' % self._noun)
         return self._handle
 
-    def _apply(self, r):
+    handle = property(lambda self: self._live(), doc="The opaque handle for libmikrylov; ValueError once freed.")
+
+    def _call(self, entry, *args):
         h = self._live()
-        r = np.ascontiguousarray(r, dtype=np.float64)
+        _lib.check(getattr(self._lib, 'mk_%s_%s' % (self._abi, entry))(h, *args))
+
+    def _read_info(self, names, *level):
+        cap = getattr(_lib, 'MK_%s_INFO_LEN' % self._abi.upper())
+        v = (ctypes.c_int64 * cap)()
+        self._call('info', *(level + (v, cap)))
+        return dict(zip(names, (int(x) for x in v)))
+
+    info = property(lambda self: self._read_info(self._info_names), doc="``mk_<kind>_info`` as a dict.")
+
+    def _times_vector(self, x):
+        self._live()                                         # (a freed object says so before anything else)
+        return LinearOperator._times_vector(self, x)
+
+    def _apply(self, r):
+        self._live()
         if self._buf is None:
             self._buf = _lib.DeviceArray(self._n, zero=False)
-        self._buf.upload(r)
-        _lib.check(self._lib.mk_ilu_apply(h, self._buf.ptr, self._buf.ptr))
+        self._buf.upload(np.ascontiguousarray(r, dtype=np.float64))
+        self._call('apply', self._buf.ptr, self._buf.ptr)
         return self._buf.to_numpy()
 
-    def factor_arrays(self):
-        """``(indptr, indices, values, diag)``: the factor on the pattern of the operator (values as described in
-        include/mikrylov.h, mk_ilu_download) and the position of each row's diagonal entry."""
-        h = self._live()
-        indptr, indices, _ = self._op.to_csr_arrays()
-        vals = np.empty(self._nnz, dtype=np.float64)
-        diag = np.empty(self._n, dtype=np.int32)
-        _lib.check(self._lib.mk_ilu_download(h, vals.ctypes.data, diag.ctypes.data))
-        return indptr, indices, vals, diag
+    def apply_device(self, d_in, d_out):
+        "``d_out = self * d_in`` on DeviceArray vectors (`d_in is d_out` allowed); enqueued on the library's stream."
+        self._live()
+        for d in (d_in, d_out):
+            if not isinstance(d, _lib.DeviceArray) or d.n != self._n or d.dtype != np.float64 or not d.ptr:
+                raise ValueError('apply_device needs live float64 DeviceArray vectors of %d entries' % self._n)
+        self._call('apply', d_in.ptr, d_out.ptr)
 
     def free(self):
-        if getattr(self, '_buf', None) is not None:
+        if self._buf is not None:
             self._buf.free()
             self._buf = None
-        if getattr(self, '_handle', None):
+        if self._handle:
             try:
-                self._lib.mk_ilu_destroy(self._handle)
+                getattr(self._lib, 'mk_%s_destroy' % self._abi)(self._handle)
             except Exception:
                 pass
             self._handle = None
@@ -249,33 +251,60 @@ class IluPreconditioner(LinearOperator):
         self.free()
 
 
+def ilu0(op):
+    """ILU(0) of a square device matrix (a :class:`CsrOperator`) as a DEVICE preconditioner: the factor is computed on the
+    GPU on the pattern of `op` (every row must store its diagonal), and ``precon * r`` -- inside a solver's loop or on a
+    NumPy vector -- is the pair of level-scheduled triangular solves ``U^-1 L^-1 r`` (mk_ilu_apply).  Passed as
+    ``precon=`` to CG / BiCGSTAB / CGS / TFQMR / MINRES / SYMMLQ it is applied at the reference's preconditioner sites
+    without a host round trip.  Raises MkError on a zero pivot (naming the row)."""
+    _device_matrix(op, 'ilu0', 'the incomplete factorizations', symmetric=False, factor=True)
+    return IluPreconditioner(op, 0)
 
-def _cheb_operator(op, what='chebyshev', noun='the Chebyshev preconditioner'):
-    """Kind / shape checks of `chebyshev` and `lanczos`, made before the device is touched (those of
-    ``_ilu_operator(symmetric=True)``)."""
-    shape = getattr(op, 'shape', None)
-    if shape is None or len(shape) != 2:
-        raise TypeError('%s needs an operator with a `.shape`; got %r' % (what, type(op).__name__))
-    from .linop import CsrOperator
-    if getattr(op, 'local_size', None) is not None:
-        raise NotImplementedError('%s: the operator is row-partitioned; %s is single-GPU' % (what, noun))
-    if not isinstance(op, CsrOperator):
-        raise TypeError('%s: %r holds no CSR arrays on the device; form its matrix (e.g. `to_csr_arrays()` of a device '
-                        'operator) and wrap it in a CsrOperator' % (what, type(op).__name__))
-    if shape[0] != shape[1]:
-        raise ValueError('%s needs a square operator, got shape %s' % (what, (shape,)))
-    if not getattr(op, 'symmetric', False):
-        raise ValueError('%s needs a symmetric operator (declared with symmetric=True)' % what)
-    return op
+
+def ic0(op):
+    """IC(0) (incomplete Cholesky, no fill) of a symmetric device matrix: ``M = L L^T`` on the lower pattern of `op`, as a
+    symmetric device preconditioner like :func:`ilu0` (MINRES' symmetry check of the preconditioner passes).  Raises
+    ValueError for an operator not declared symmetric, MkError for a pattern that is not symmetric or a pivot that is not
+    positive (naming the row)."""
+    _device_matrix(op, 'ic0', 'the incomplete factorizations', factor=True)
+    return IluPreconditioner(op, 1)
+
+
+class IluPreconditioner(DevicePreconditioner):
+    """M^-1 of an ILU(0) / IC(0) factor resident in HBM (`ilu0`, `ic0`), a :class:`DevicePreconditioner`.  Attributes: `kind`
+    ('ilu0' / 'ic0'), `levels` and `launches` (forward, backward sweep), `info` (mk_ilu_info as a dict)."""
+
+    route, plural, _noun, _abi = 'ilu', 'incomplete factorizations', 'the factor', 'ilu'
+    _info_names = ('kind', 'rows', 'nnz', 'levels_forward', 'levels_backward', 'launches_forward', 'launches_backward',
+                   'widest_level', 'bytes', 'fuse_rows', 'analysis_us', 'factor_us')
+
+    def __init__(self, op, kind):
+        lib = _lib.init()
+        h = ctypes.c_void_p()
+        fn = lib.mk_ic0_create if kind else lib.mk_ilu0_create
+        _lib.check(fn(op.handle, ctypes.byref(h)))
+        self._nnz = int(op.nnz)
+        self.kind = 'ic0' if kind else 'ilu0'
+        self._attach(h.value, op.shape[0], bool(kind), op)   # (`op`: its pattern; factor_arrays() pairs it with the values)
+
+    levels = property(lambda self: (self.info['levels_forward'], self.info['levels_backward']))
+    launches = property(lambda self: (self.info['launches_forward'], self.info['launches_backward']))
+
+    def factor_arrays(self):
+        """``(indptr, indices, values, diag)``: the factor on the pattern of the operator (values as described in
+        include/mikrylov.h, mk_ilu_download) and the position of each row's diagonal entry."""
+        self._live()
+        indptr, indices, _ = self._op.to_csr_arrays()
+        vals = np.empty(self._nnz, dtype=np.float64)
+        diag = np.empty(self._n, dtype=np.int32)
+        self._call('download', vals.ctypes.data, diag.ctypes.data)
+        return indptr, indices, vals, diag
 
 
 def _lanczos_args(what, steps, seed):
     """`steps` and `seed` of `lanczos` (and of ``chebyshev(interval='lanczos')``), checked before the device is touched."""
-    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or int(steps) < 1 or int(steps) >= 2 ** 31:
-        raise ValueError('%s: steps must be a positive integer, got %r' % (what, steps))
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError('%s: seed must be an integer from 0 to 2**64 - 1, got %r' % (what, seed))
-    return int(steps), int(seed)
+    return (_checked_int(what, 'steps', steps, 1, 2 ** 31 - 1, 'a positive integer'),
+            _checked_int(what, 'seed', seed, 0, 2 ** 64 - 1, 'an integer from 0 to 2**64 - 1'))
 
 
 class LanczosResult(object):
@@ -310,7 +339,7 @@ def lanczos(op, steps=10, scale_diag=False, seed=1, start=None):
     of ones, which is orthogonal to the top eigenvector of ``poisson2d(m)`` for even m.  The run stops early at a breakdown
     (`steps` then reads less than asked for: the Ritz values are eigenvalues).  No reorthogonalisation; do not go below the
     default of 10 steps for an upper bound that is to hold."""
-    _cheb_operator(op, 'lanczos', 'the Lanczos estimate')
+    _device_matrix(op, 'lanczos', 'the Lanczos estimate')
     steps, seed = _lanczos_args('lanczos', steps, seed)
     n = int(op.shape[0])
     if n == 0:
@@ -356,13 +385,10 @@ def chebyshev(op, degree=4, lmin=None, lmax=None, ratio=30.0, scale_diag=False, 
     Krylov space held one eigenvalue only, ``lmin = lmax / ratio``.  It costs `steps` products and stream passes once, and is
     not always the better interval, hence opt-in.  `interval_source` of the result names, per end, where it
     came from: ``'gershgorin'``, ``'lanczos'`` or ``'given'``."""
-    _cheb_operator(op)
+    _device_matrix(op, 'chebyshev', 'the Chebyshev preconditioner')
     if interval not in ('gershgorin', 'lanczos'):
         raise ValueError("chebyshev: interval must be 'gershgorin' or 'lanczos', got %r" % (interval,))
-    if isinstance(degree, bool) or not isinstance(degree, (int, np.integer)):
-        raise ValueError('chebyshev: degree must be an integer from 1 to %d, got %r' % (_lib.MK_CHEB_MAX_DEGREE, degree))
-    if not 1 <= int(degree) <= _lib.MK_CHEB_MAX_DEGREE:
-        raise ValueError('chebyshev: degree must be an integer from 1 to %d, got %r' % (_lib.MK_CHEB_MAX_DEGREE, degree))
+    degree = _checked_int('chebyshev', 'degree', degree, 1, _lib.MK_CHEB_MAX_DEGREE)
     for name, v in (('lmin', lmin), ('lmax', lmax)):
         if v is not None and not (np.isfinite(v) and v > 0):
             raise ValueError('chebyshev: %s must be positive and finite, got %r' % (name, v))
@@ -389,26 +415,23 @@ def chebyshev(op, degree=4, lmin=None, lmax=None, ratio=30.0, scale_diag=False, 
         if not lmin < lmax:
             raise ValueError('chebyshev: the interval needs 0 < lmin < lmax, got lmin = %r, lmax = %r (Lanczos bounds %r)'
                              % (lmin, lmax, (lo, hi)))
-    M = ChebyshevPreconditioner(op, int(degree), lmin, lmax, float(ratio), bool(scale_diag))
+    M = ChebyshevPreconditioner(op, degree, lmin, lmax, float(ratio), bool(scale_diag))
     M.interval_source = source
     M.lanczos = estimate
     return M
 
 
-class ChebyshevPreconditioner(LinearOperator):
-    """``p_k(A)`` of a symmetric device matrix, resident in HBM (`chebyshev`).  ``self * v`` applies it to a NumPy vector,
-    `apply_device` to DeviceArray vectors; solvers given it as ``precon=`` (``M=`` / ``N=``) apply it on the device
-    (mk_solver_set_precon_cheb / mk_solver_set_lls_precon_cheb).  Attributes: `degree`, `interval` (``(lmin, lmax)`` as
-    used), `interval_source` (per end ``'gershgorin'``, ``'lanczos'`` or ``'given'``), `lanczos` (the :class:`LanczosResult`
-    behind ``interval='lanczos'``, else None), `coefficients` (``c0`` and the arrays ``c1``, ``c2`` of the steps), `scaled`,
-    `info` (mk_cheb_info as a dict).  `free()` releases this object's reference; a solver that still applies the object keeps it alive."""
+class ChebyshevPreconditioner(DevicePreconditioner):
+    """``p_k(A)`` of a symmetric device matrix, resident in HBM (`chebyshev`), a :class:`DevicePreconditioner`.  Attributes:
+    `degree`, `interval` (``(lmin, lmax)`` as used), `interval_source` (per end ``'gershgorin'``, ``'lanczos'`` or
+    ``'given'``), `lanczos` (the :class:`LanczosResult` behind ``interval='lanczos'``, else None), `coefficients` (``c0`` and
+    the arrays ``c1``, ``c2`` of the steps), `scaled`, `info` (mk_cheb_info as a dict)."""
+
+    route, plural, _noun, _abi = 'cheb', 'Chebyshev preconditioners', 'the Chebyshev preconditioner', 'cheb'
+    _info_names = ('rows', 'degree', 'scaled', 'launches', 'bytes', 'setup_us', 'lmin_default', 'lmax_default')
 
     def __init__(self, op, degree, lmin, lmax, ratio, scale_diag):
-        lib = _lib.init()
-        self._lib = lib
-        self._handle = None
-        self._buf = None
-        self._n = int(op.shape[0])
+        lib = self._lib = _lib.init()
         self.degree = int(degree)
         self.scaled = bool(scale_diag)
         self.interval_source = tuple('gershgorin' if v is None else 'given' for v in (lmin, lmax))
@@ -422,9 +445,8 @@ class ChebyshevPreconditioner(LinearOperator):
                 lmin = self._coefficients(probe, 1)[1] / ratio
             finally:
                 lib.mk_cheb_destroy(probe)
-        self._handle = self._create(op, self.degree, 0.0 if lmin is None else float(lmin), 0.0 if lmax is None else float(lmax))
-        self._op = op                      # (keeps the matrix's Python owner alive beside the library's own count)
-        LinearOperator.__init__(self, self._n, self._n, matvec=self._apply, symmetric=True, dtype=np.float64)
+        h = self._create(op, self.degree, 0.0 if lmin is None else float(lmin), 0.0 if lmax is None else float(lmax))
+        self._attach(h, op.shape[0], True, op)
 
     def _create(self, op, degree, lmin, lmax):
         h = ctypes.c_void_p()
@@ -435,15 +457,6 @@ class ChebyshevPreconditioner(LinearOperator):
         v = (ctypes.c_double * (3 + 2 * degree))()
         _lib.check(self._lib.mk_cheb_coefficients(handle, v))
         return np.array(v[:], dtype=np.float64)
-
-    handle = property(lambda self: self._live(), doc="Opaque ``mk_cheb*`` for libmikrylov.")
-
-    @property
-    def info(self):
-        names = ('rows', 'degree', 'scaled', 'launches', 'bytes', 'setup_us', 'lmin_default', 'lmax_default')
-        v = (ctypes.c_int64 * _lib.MK_CHEB_INFO_LEN)()
-        _lib.check(self._lib.mk_cheb_info(self._live(), v, _lib.MK_CHEB_INFO_LEN))
-        return dict(zip(names, (int(x) for x in v)))
 
     @property
     def interval(self):
@@ -456,42 +469,6 @@ class ChebyshevPreconditioner(LinearOperator):
         "``(c0, c1, c2)``: the scalar of the first direction and the two coefficient arrays of the steps 1 .. degree."
         c = self._coefficients(self._live(), self.degree)
         return float(c[2]), c[3::2].copy(), c[4::2].copy()
-
-    def _live(self):
-        if not self._handle:
-            raise ValueError('the Chebyshev preconditioner has been freed')
-        return self._handle
-
-    def _apply(self, r):
-        h = self._live()
-        r = np.ascontiguousarray(r, dtype=np.float64)
-        if self._buf is None:
-            self._buf = _lib.DeviceArray(self._n, zero=False)
-        self._buf.upload(r)
-        _lib.check(self._lib.mk_cheb_apply(h, self._buf.ptr, self._buf.ptr))
-        return self._buf.to_numpy()
-
-    def apply_device(self, d_in, d_out):
-        "``d_out = p_k(A) d_in`` on DeviceArray vectors (`d_in is d_out` allowed); enqueued on the library's stream."
-        for d in (d_in, d_out):
-            if not isinstance(d, _lib.DeviceArray) or d.n != self._n or d.dtype != np.float64 or not d.ptr:
-                raise ValueError('apply_device needs live float64 DeviceArray vectors of %d entries' % self._n)
-        _lib.check(self._lib.mk_cheb_apply(self._live(), d_in.ptr, d_out.ptr))
-
-    def free(self):
-        if getattr(self, '_buf', None) is not None:
-            self._buf.free()
-            self._buf = None
-        if getattr(self, '_handle', None):
-            try:
-                self._lib.mk_cheb_destroy(self._handle)
-            except Exception:
-                pass
-            self._handle = None
-        self._op = None
-
-    def __del__(self):
-        self.free()
 
 
 def _pattern_power(indptr, indices, n, power):
@@ -532,10 +509,8 @@ def fsai(op, power=1, pattern=None):
     the row otherwise.  Passed as ``precon=`` to CG / BiCGSTAB / CGS / TFQMR / MINRES / SYMMLQ / GMRES, or as ``M=`` / ``N=``
     to the least-squares solvers, it is applied without a host round trip.  Raises MkError naming the row for a pattern that
     is not as described, a row without a stored diagonal entry and a breakdown (the matrix is not positive definite)."""
-    _cheb_operator(op, 'fsai', 'the FSAI preconditioner')
-    if isinstance(power, bool) or not isinstance(power, (int, np.integer)) or not 1 <= int(power) <= 3:
-        raise ValueError('fsai: power must be 1, 2 or 3, got %r' % (power,))
-    power = int(power)
+    _device_matrix(op, 'fsai', 'the FSAI preconditioner')
+    power = _checked_int('fsai', 'power', power, 1, 3, '1, 2 or 3')
     n = int(op.shape[0])
     if pattern is not None:
         if power != 1:
@@ -565,19 +540,15 @@ def fsai(op, power=1, pattern=None):
     return FsaiPreconditioner(op, power, pattern)
 
 
-class FsaiPreconditioner(LinearOperator):
-    """``G^T G`` of an FSAI factor resident in HBM (`fsai`).  ``self * v`` applies it to a NumPy vector, `apply_device` to
-    DeviceArray vectors; solvers given it as ``precon=`` (``M=`` / ``N=``) apply it on the device
-    (mk_solver_set_precon_fsai / mk_solver_set_lls_precon_fsai).  Attributes: `power`, `info` (mk_fsai_info as a dict).
-    `factor_arrays()` downloads G.  The object does not keep the matrix it was computed from.  `free()` releases this
-    object's reference; a solver that still applies the object keeps it alive."""
+class FsaiPreconditioner(DevicePreconditioner):
+    """``G^T G`` of an FSAI factor resident in HBM (`fsai`), a :class:`DevicePreconditioner`.  Attributes: `power`, `info`
+    (mk_fsai_info as a dict).  `factor_arrays()` downloads G.  The object does not keep the matrix it was computed from."""
+
+    route, plural, _noun, _abi = 'fsai', 'FSAI preconditioners', 'the FSAI preconditioner', 'fsai'
+    _info_names = ('rows', 'nnz', 'longest_row', 'launches', 'bytes', 'format_g', 'format_gt', 'setup_us')
 
     def __init__(self, op, power=1, pattern=None):
         lib = _lib.init()
-        self._lib = lib
-        self._handle = None
-        self._buf = None
-        self._n = int(op.shape[0])
         self.power = int(power)
         h = ctypes.c_void_p()
         ip, ix = (None, None) if pattern is None else pattern
@@ -588,75 +559,23 @@ class FsaiPreconditioner(LinearOperator):
             if 'more than MK_FSAI_MAX_ROW' in msg:           # (the pattern came from the device: power = 1)
                 raise ValueError('fsai: %s: lower `power` (or give a sparser `pattern`)' % msg.split(': ', 1)[-1])
             _lib.check(rc)
-        self._handle = h.value
-        LinearOperator.__init__(self, self._n, self._n, matvec=self._apply, symmetric=True, dtype=np.float64)
-
-    handle = property(lambda self: self._live(), doc="Opaque ``mk_fsai*`` for libmikrylov.")
-
-    @property
-    def info(self):
-        names = ('rows', 'nnz', 'longest_row', 'launches', 'bytes', 'format_g', 'format_gt', 'setup_us')
-        v = (ctypes.c_int64 * _lib.MK_FSAI_INFO_LEN)()
-        _lib.check(self._lib.mk_fsai_info(self._live(), v, _lib.MK_FSAI_INFO_LEN))
-        return dict(zip(names, (int(x) for x in v)))
-
-    def _live(self):
-        if not self._handle:
-            raise ValueError('the FSAI preconditioner has been freed')
-        return self._handle
-
-    def _apply(self, r):
-        h = self._live()
-        r = np.ascontiguousarray(r, dtype=np.float64)
-        if self._buf is None:
-            self._buf = _lib.DeviceArray(self._n, zero=False)
-        self._buf.upload(r)
-        _lib.check(self._lib.mk_fsai_apply(h, self._buf.ptr, self._buf.ptr))
-        return self._buf.to_numpy()
-
-    def apply_device(self, d_in, d_out):
-        "``d_out = G^T (G d_in)`` on DeviceArray vectors (`d_in is d_out` allowed); enqueued on the library's stream."
-        for d in (d_in, d_out):
-            if not isinstance(d, _lib.DeviceArray) or d.n != self._n or d.dtype != np.float64 or not d.ptr:
-                raise ValueError('apply_device needs live float64 DeviceArray vectors of %d entries' % self._n)
-        _lib.check(self._lib.mk_fsai_apply(self._live(), d_in.ptr, d_out.ptr))
+        self._attach(h.value, op.shape[0], True)
 
     def factor_arrays(self):
         "``(indptr, indices, values)`` of G: lower triangular CSR, every row ending with its diagonal entry."
-        h = self._live()
         nnz = self.info['nnz']
         indptr = np.empty(self._n + 1, dtype=np.int32)
         indices = np.empty(nnz, dtype=np.int32)
         values = np.empty(nnz, dtype=np.float64)
-        _lib.check(self._lib.mk_fsai_download(h, indptr.ctypes.data, indices.ctypes.data, values.ctypes.data))
+        self._call('download', indptr.ctypes.data, indices.ctypes.data, values.ctypes.data)
         return indptr, indices, values
 
     def factor_handles(self):
         """Borrowed ``mk_csr*`` handles of G and of its transpose, for ``mk_csr_set_format`` / ``mk_csr_format_info``; they
         belong to this object."""
         g, gt = ctypes.c_void_p(), ctypes.c_void_p()
-        _lib.check(self._lib.mk_fsai_factors(self._live(), ctypes.byref(g), ctypes.byref(gt)))
+        self._call('factors', ctypes.byref(g), ctypes.byref(gt))
         return g.value, gt.value
-
-    def free(self):
-        if getattr(self, '_buf', None) is not None:
-            self._buf.free()
-            self._buf = None
-        if getattr(self, '_handle', None):
-            try:
-                self._lib.mk_fsai_destroy(self._handle)
-            except Exception:
-                pass
-            self._handle = None
-
-    def __del__(self):
-        self.free()
-
-
-def _amg_int(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-        raise ValueError('amg: %s must be an integer from %d to %d, got %r' % (name, lo, hi, v))
-    return int(v)
 
 
 def _amg_real(name, v, ok, what):
@@ -678,32 +597,30 @@ def amg(op, theta=0.0, degree=1, ratio=4.0, omega=4.0 / 3.0, coarse_max=256, max
     ``[lmax / ratio, lmax]`` (`chebyshev`).  Passed as ``precon=`` to CG / BiCGSTAB / CGS / TFQMR / MINRES / SYMMLQ / GMRES /
     IDR, or as ``M=`` / ``N=`` to the least-squares solvers, it is applied without a host round trip.  ValueError naming the
     row for a diagonal entry that is missing, zero or negative (on any level)."""
-    _cheb_operator(op, 'amg', 'the AMG preconditioner')
+    _device_matrix(op, 'amg', 'the AMG preconditioner')
     theta = _amg_real('theta', theta, lambda v: v >= 0.0, '>= 0')
     ratio = _amg_real('ratio', ratio, lambda v: v > 1.0, '> 1')
     omega = _amg_real('omega', omega, lambda v: v > 0.0, '> 0')
-    degree = _amg_int('degree', degree, 1, _lib.MK_CHEB_MAX_DEGREE)
-    coarse_max = _amg_int('coarse_max', coarse_max, 1, _lib.MK_AMG_MAX_COARSE)
-    max_levels = _amg_int('max_levels', max_levels, 1, _lib.MK_AMG_MAX_LEVELS)
-    seed = _amg_int('seed', seed, 0, 2 ** 64 - 1)
-    expand_cap = _amg_int('expand_cap', expand_cap, 0, 2 ** 31 - 1)
+    degree = _checked_int('amg', 'degree', degree, 1, _lib.MK_CHEB_MAX_DEGREE)
+    coarse_max = _checked_int('amg', 'coarse_max', coarse_max, 1, _lib.MK_AMG_MAX_COARSE)
+    max_levels = _checked_int('amg', 'max_levels', max_levels, 1, _lib.MK_AMG_MAX_LEVELS)
+    seed = _checked_int('amg', 'seed', seed, 0, 2 ** 64 - 1)
+    expand_cap = _checked_int('amg', 'expand_cap', expand_cap, 0, 2 ** 31 - 1)
     return AmgPreconditioner(op, theta, degree, ratio, omega, coarse_max, max_levels, seed, expand_cap)
 
 
-class AmgPreconditioner(LinearOperator):
-    """One V(1,1)-cycle of a smoothed-aggregation hierarchy resident in HBM (`amg`).  ``self * v`` applies it to a NumPy
-    vector, `apply_device` to DeviceArray vectors; solvers given it as ``precon=`` (``M=`` / ``N=``) apply it on the device
-    (mk_solver_set_precon_amg / mk_solver_set_lls_precon_amg).  Attributes: `info` (the totals of mk_amg_info as a dict),
-    `levels` (one dict per level), `operator_complexity`, `grid_complexity`; `level_arrays(l)` downloads a level,
-    `coarse_inverse()` the dense inverse of the last one, `level_handles(l)` gives the borrowed ``mk_csr*`` of a level.
-    `free()` releases this object's reference; a solver that still applies the object keeps it alive."""
+class AmgPreconditioner(DevicePreconditioner):
+    """One V(1,1)-cycle of a smoothed-aggregation hierarchy resident in HBM (`amg`), a :class:`DevicePreconditioner`.
+    Attributes: `info` (the totals of mk_amg_info as a dict), `levels` (one dict per level), `operator_complexity`,
+    `grid_complexity`; `level_arrays(l)` downloads a level, `coarse_inverse()` the dense inverse of the last one,
+    `level_handles(l)` gives the borrowed ``mk_csr*`` of a level."""
+
+    route, plural, _noun, _abi = 'amg', 'AMG preconditioners', 'the AMG preconditioner', 'amg'
+    _info_names = ('levels', 'bytes', 'setup_us', 'launches', 'coarse_dense', 'operator_complexity_x1000',
+                   'grid_complexity_x1000', 'nnz_total', 'rows_total', 'coarse_why')
 
     def __init__(self, op, theta, degree, ratio, omega, coarse_max, max_levels, seed, expand_cap):
         lib = _lib.init()
-        self._lib = lib
-        self._handle = None
-        self._buf = None
-        self._n = int(op.shape[0])
         self.params = dict(theta=theta, degree=degree, ratio=ratio, omega=omega, coarse_max=coarse_max,
                            max_levels=max_levels, seed=seed, expand_cap=expand_cap)
         h = ctypes.c_void_p()
@@ -713,21 +630,15 @@ class AmgPreconditioner(LinearOperator):
             if 'has no positive diagonal entry' in msg:
                 raise ValueError('amg: %s' % msg.split(': ', 1)[-1])
             _lib.check(rc)
-        self._handle = h.value
-        self._op = op                      # (keeps the matrix's Python owner alive beside the library's own count)
-        LinearOperator.__init__(self, self._n, self._n, matvec=self._apply, symmetric=True, dtype=np.float64)
-
-    handle = property(lambda self: self._live(), doc="Opaque ``mk_amg*`` for libmikrylov.")
+        self._attach(h.value, op.shape[0], True, op)
 
     def _info(self, level, names):
-        v = (ctypes.c_int64 * _lib.MK_AMG_INFO_LEN)()
-        _lib.check(self._lib.mk_amg_info(self._live(), level, v, _lib.MK_AMG_INFO_LEN))
-        return dict(zip(names, (int(x) for x in v)))
+        "mk_amg_info takes a level: -1 the totals, else the level's figures."
+        return self._read_info(names, level)
 
     @property
     def info(self):
-        d = self._info(-1, ('levels', 'bytes', 'setup_us', 'launches', 'coarse_dense', 'operator_complexity_x1000',
-                            'grid_complexity_x1000', 'nnz_total', 'rows_total', 'coarse_why'))
+        d = self._info(-1, self._info_names)
         d['coarse_solver'] = 'inverse' if d['coarse_dense'] else 'smoother'
         return d
 
@@ -739,7 +650,7 @@ class AmgPreconditioner(LinearOperator):
         for l in range(self.info['levels']):
             d = self._info(l, names)
             lmax = ctypes.c_double()
-            _lib.check(self._lib.mk_amg_download(self._live(), l, None, ctypes.byref(lmax)))
+            self._call('download', l, None, ctypes.byref(lmax))
             d['lmax'] = lmax.value
             out.append(d)
         return out
@@ -753,27 +664,6 @@ class AmgPreconditioner(LinearOperator):
     def grid_complexity(self):
         return self.info['rows_total'] / float(self._n or 1)
 
-    def _live(self):
-        if not self._handle:
-            raise ValueError('the AMG preconditioner has been freed')
-        return self._handle
-
-    def _apply(self, r):
-        h = self._live()
-        r = np.ascontiguousarray(r, dtype=np.float64)
-        if self._buf is None:
-            self._buf = _lib.DeviceArray(self._n, zero=False)
-        self._buf.upload(r)
-        _lib.check(self._lib.mk_amg_apply(h, self._buf.ptr, self._buf.ptr))
-        return self._buf.to_numpy()
-
-    def apply_device(self, d_in, d_out):
-        "``d_out`` = one V-cycle on ``d_in``, DeviceArray vectors (`d_in is d_out` allowed); enqueued on the library's stream."
-        for d in (d_in, d_out):
-            if not isinstance(d, _lib.DeviceArray) or d.n != self._n or d.dtype != np.float64 or not d.ptr:
-                raise ValueError('apply_device needs live float64 DeviceArray vectors of %d entries' % self._n)
-        _lib.check(self._lib.mk_amg_apply(self._live(), d_in.ptr, d_out.ptr))
-
     def level_handles(self, level):
         """Borrowed ``mk_csr*`` handles ``(A_l, P, R)`` of a level, for ``mk_csr_set_format`` / ``mk_csr_format_info``; P and R
         are None on the last level.  They belong to this object."""
@@ -784,7 +674,7 @@ class AmgPreconditioner(LinearOperator):
                 out.append(None)
                 continue
             h = ctypes.c_void_p()
-            _lib.check(self._lib.mk_amg_level(self._live(), level, which, ctypes.byref(h)))
+            self._call('level', level, which, ctypes.byref(h))
             out.append(h.value)
         return tuple(out)
 
@@ -806,10 +696,10 @@ class AmgPreconditioner(LinearOperator):
         if p is not None:
             out['P'], out['R'] = self._csr_arrays(p), self._csr_arrays(r)
             agg = np.empty(out['A'][3][0], dtype=np.int32)
-            _lib.check(self._lib.mk_amg_download(self._live(), level, agg.ctypes.data, ctypes.byref(lmax)))
+            self._call('download', level, agg.ctypes.data, ctypes.byref(lmax))
             out['agg'] = agg
         else:
-            _lib.check(self._lib.mk_amg_download(self._live(), level, None, ctypes.byref(lmax)))
+            self._call('download', level, None, ctypes.byref(lmax))
         out['lmax'] = lmax.value
         return out
 
@@ -819,20 +709,5 @@ class AmgPreconditioner(LinearOperator):
             return None
         n = self._info(self.info['levels'] - 1, ('rows',))['rows']
         inv = np.empty((n, n), dtype=np.float64)
-        _lib.check(self._lib.mk_amg_coarse(self._live(), inv.ctypes.data))
+        self._call('coarse', inv.ctypes.data)
         return inv
-
-    def free(self):
-        if getattr(self, '_buf', None) is not None:
-            self._buf.free()
-            self._buf = None
-        if getattr(self, '_handle', None):
-            try:
-                self._lib.mk_amg_destroy(self._handle)
-            except Exception:
-                pass
-            self._handle = None
-        self._op = None
-
-    def __del__(self):
-        self.free()

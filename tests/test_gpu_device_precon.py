@@ -232,3 +232,85 @@ def test_every_setter_replaces_whatever_preconditioner_was_attached(solver):
     d_dinv.free()
     op.free()
     Mop.free()
+
+
+# ------------------------------------------------------------------ the device preconditioner OBJECTS, one body for all kinds
+# (kind, how `tools` makes it, the solver that takes it, the launch counters of `info` and their values per matrix:
+#  launches per apply, read from the commit before the objects got their common base -- neither the kernels nor their
+#  order may change)
+OBJECTS = {
+    "ilu0": (lambda tools, op: tools.ilu0(op), "bicgstab", ("launches_forward", "launches_backward"), {64: (1, 1), 1: (1, 1)}),
+    "ic0": (lambda tools, op: tools.ic0(op), "pcg", ("launches_forward", "launches_backward"), {64: (1, 1), 1: (1, 1)}),
+    "chebyshev": (lambda tools, op: tools.chebyshev(op, degree=3), "pcg", ("launches",), {64: (4,), 1: (4,)}),
+    "fsai": (lambda tools, op: tools.fsai(op), "pcg", ("launches",), {64: (2,), 1: (2,)}),
+    "amg": (lambda tools, op: tools.amg(op, coarse_max=8), "pcg", ("launches",), {64: (19,), 1: (1,)}),
+}
+# counters of `info` that count applies and so may differ before and after a solve: none of these five kinds has one
+# (`applies` and `launches_last_apply` of an L-BFGS operator would be named here)
+APPLY_COUNTERS = ()
+
+
+@pytest.mark.parametrize("n", [64, 1])
+@pytest.mark.parametrize("kind", sorted(OBJECTS))
+def test_device_objects_share_one_apply_path_and_one_lifetime(kind, n):
+    """poisson2d(8) and the 1 x 1 matrix [[2.0]] (`tools.amg` takes it too: one level, its dense inverse).  (1) ``M * v``,
+    `apply_device` out of place and in place agree bit for bit; (2) after a solve that ran to convergence -- its loop has
+    halted -- ``M * v`` has the bits it had before: the standalone apply reads the object's own never-raised words, not the
+    solver's; (3) `info` without its times is what it was; (4) freed twice while a solver holds it, the solve gives the bits
+    of the solve with the live object, and afterwards ``M * v`` raises."""
+    from pykrylov_amd import CsrOperator, _lib, tools
+    from pykrylov_amd.generic import DeviceRun
+    make, solver, counters, launches = OBJECTS[kind]
+    if n == 1:
+        indptr, indices, data, shape = np.array([0, 1]), np.array([0]), np.array([2.0]), (1, 1)
+        rhs = np.array([2.0])
+    else:
+        A = csr_ref.poisson2d(8)
+        indptr, indices, data, shape = A.indptr, A.indices, A.data, A.shape
+        rhs = A.matvec(np.ones(n))
+    op = CsrOperator(indptr, indices, data, shape, symmetric=True)
+    M = make(tools, op)
+    v = np.random.default_rng(5).standard_normal(n)
+
+    def counts():
+        return {k: c for k, c in M.info.items() if not k.endswith("_us") and k not in APPLY_COUNTERS}
+
+    def new_run():
+        extra = dict(check_curvature=1, pcg=(False,)) if solver == "pcg" else {}
+        return DeviceRun(op, _lib.MK_PCG if solver == "pcg" else _lib.MK_BICGSTAB, rhs, None, precon_diag=M, abstol=0.0,
+                         reltol=1e-10, matvec_max=200, **extra)
+
+    def solve(run):
+        res = run.run()
+        x = run.x()
+        assert res.halted and res.converged and res.nMatvec >= 1 and np.all(np.isfinite(x)), (kind, n)
+        run.close()
+        return x
+
+    # (1)
+    y = M * v
+    assert y.shape == (n,) and np.all(np.isfinite(y)) and np.any(y != v)
+    d_in, d_out = _lib.DeviceArray.from_numpy(v), _lib.DeviceArray(n)
+    M.apply_device(d_in, d_out)
+    assert np.array_equal(d_out.to_numpy(), y) and np.array_equal(d_in.to_numpy(), v)
+    M.apply_device(d_in, d_in)
+    assert np.array_equal(d_in.to_numpy(), y)
+    d_in.free()
+    d_out.free()
+    before = counts()
+    print("%s n = %d: %s" % (kind, n, before))
+    assert tuple(before[c] for c in counters) == launches[n]
+    # (2), (3)
+    run = new_run()
+    assert run.precon_kind == M.route
+    x_live = solve(run)
+    assert np.array_equal(M * v, y)
+    assert counts() == before
+    # (4)
+    run = new_run()
+    M.free()
+    M.free()
+    assert np.array_equal(solve(run), x_live)
+    with pytest.raises(ValueError, match="freed"):
+        M * v
+    op.free()

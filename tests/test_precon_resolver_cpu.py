@@ -5,10 +5,40 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests.test_host import header_functions
+
 N = 10
 NAMES = ("precon", "M", "N")
-KINDS = ("none", "diag", "host", "device", "ilu", "lbfgs", "cheb")
-SINGLE_GPU = ("host", "ilu", "lbfgs", "cheb")
+KINDS = ("none", "diag", "host", "device", "ilu", "lbfgs", "cheb", "fsai", "amg")
+SINGLE_GPU = ("host", "ilu", "lbfgs", "cheb", "fsai", "amg")
+OBJECT_CLASSES = ("IluPreconditioner", "ChebyshevPreconditioner", "FsaiPreconditioner", "AmgPreconditioner")
+
+# the functions include/mikrylov.h declares, as of the commit before the device objects got their common base
+ABI = """
+    mk_amg_apply mk_amg_coarse mk_amg_create mk_amg_destroy mk_amg_download mk_amg_info mk_amg_level
+    mk_arena_reserve mk_axpby mk_axpy mk_build_info mk_calib_stream mk_cheb_apply mk_cheb_coefficients
+    mk_cheb_create mk_cheb_destroy mk_cheb_info mk_comm_allreduce_host mk_comm_destroy mk_comm_info mk_comm_init
+    mk_comm_init_host mk_comm_time_allreduce mk_comm_time_exchange mk_comm_transport mk_comm_unique_id
+    mk_csr_col_range mk_csr_colblocks mk_csr_comm_last_us mk_csr_compose mk_csr_create mk_csr_create_block
+    mk_csr_create_callback mk_csr_create_product mk_csr_create_reduced mk_csr_create_sum mk_csr_destroy
+    mk_csr_download mk_csr_download_rows mk_csr_format_info mk_csr_from_coo mk_csr_lanczos mk_csr_launch_info
+    mk_csr_localize mk_csr_march_info mk_csr_overlap_info mk_csr_pencil_info mk_csr_poisson2d mk_csr_poisson3d
+    mk_csr_poisson3d_varcoef mk_csr_set_colblocks mk_csr_set_exchange mk_csr_set_format mk_csr_set_row_block
+    mk_csr_set_tile_order mk_csr_shape mk_csr_stencil27 mk_csr_tile_order mk_csr_transpose mk_device_info mk_dot
+    mk_exchange mk_free mk_fsai_apply mk_fsai_create mk_fsai_destroy mk_fsai_download mk_fsai_factors mk_fsai_info
+    mk_ic0_create mk_ilu0_create mk_ilu_apply mk_ilu_destroy mk_ilu_download mk_ilu_info mk_init mk_last_error
+    mk_lbfgs_apply mk_lbfgs_create mk_lbfgs_destroy mk_lbfgs_download mk_lbfgs_forward_combine mk_lbfgs_forward_dots
+    mk_lbfgs_gram mk_lbfgs_info mk_lbfgs_restart mk_lbfgs_store mk_malloc mk_memcpy_d2d mk_memcpy_d2h mk_memcpy_h2d
+    mk_memset mk_nrm2 mk_scal mk_shutdown mk_solver_create mk_solver_destroy mk_solver_finish mk_solver_fused
+    mk_solver_history mk_solver_history2 mk_solver_iterate mk_solver_set_idr mk_solver_set_lls_precon
+    mk_solver_set_lls_precon_amg mk_solver_set_lls_precon_bfgs mk_solver_set_lls_precon_callback
+    mk_solver_set_lls_precon_cheb mk_solver_set_lls_precon_csr mk_solver_set_lls_precon_fsai
+    mk_solver_set_lls_precon_ilu mk_solver_set_pcg mk_solver_set_precon_amg mk_solver_set_precon_callback
+    mk_solver_set_precon_cheb mk_solver_set_precon_csr mk_solver_set_precon_diag mk_solver_set_precon_fsai
+    mk_solver_set_precon_ilu mk_solver_set_precon_lbfgs mk_solver_set_transpose mk_solver_setup mk_solver_solve
+    mk_solver_time_product mk_solver_time_spmv mk_solver_timing mk_solver_unapplied mk_solver_vector mk_solver_x
+    mk_spmv mk_sync mk_version
+""".split()
 
 
 def _fake(cls, n):
@@ -51,7 +81,8 @@ def make(kind, n=N):
     from pykrylov_amd import tools
     return {"none": lambda: None, "diag": lambda: Diag(n), "host": lambda: Host(n), "device": lambda: Composite(n),
             "ilu": lambda: _fake(tools.IluPreconditioner, n), "lbfgs": lambda: pykrylov_amd.InverseLBFGSOperator(n),
-            "cheb": lambda: _fake(tools.ChebyshevPreconditioner, n)}[kind]()
+            "cheb": lambda: _fake(tools.ChebyshevPreconditioner, n), "fsai": lambda: _fake(tools.FsaiPreconditioner, n),
+            "amg": lambda: _fake(tools.AmgPreconditioner, n)}[kind]()
 
 
 class Op(object):
@@ -184,3 +215,43 @@ def test_the_first_error_of_a_host_thunk_is_kept():
         hp = resolve_precon(P, N, name, "Solver")[1]
         assert call_thunk(hp, np.ones(N))[0] == 1 and call_thunk(hp, np.ones(N))[0] == 1
         assert len(raised) == 2 and hp.error is raised[0] and hp.calls == 0
+
+
+@pytest.mark.parametrize("name", OBJECT_CLASSES)
+def test_a_freed_device_object_says_so_without_touching_the_device(name, monkeypatch):
+    from pykrylov_amd import _lib, tools
+
+    def no_device(*a, **k):
+        raise AssertionError("the device was touched")
+    monkeypatch.setattr(_lib, "init", no_device)
+    monkeypatch.setattr(_lib, "load", no_device)
+    P = _fake(getattr(tools, name), N)
+    P._handle = None
+    for use in (lambda: P.handle, P._live, lambda: P * np.ones(N), lambda: P.apply_device(None, None), lambda: P.info):
+        with pytest.raises(ValueError, match="freed"):
+            use()
+    P.free()
+    P.free()
+    assert P._handle is None
+
+
+def test_the_route_table_names_the_setters_of_every_route():
+    """`generic.PRECON_SETTERS` has exactly the route words `resolve_precon` can return (`make` builds one preconditioner
+    per word) except 'none', and every setter name it forms is declared in include/mikrylov.h and in `_lib.PROTOTYPES`."""
+    from pykrylov_amd import _lib
+    from pykrylov_amd.generic import PRECON_SETTERS, precon_setter, resolve_precon
+    routes = {resolve_precon(make(kind), N, "precon", "Solver")[0] for kind in KINDS}
+    assert routes == set(KINDS) and set(PRECON_SETTERS) == routes - {"none"}
+    declared = header_functions()
+    formed = [precon_setter(route, lls) for route in PRECON_SETTERS for lls in (False, True)]
+    for fn in formed:
+        assert fn in declared and fn in _lib.PROTOTYPES, fn
+    assert len(set(formed)) == len(formed)
+    # ... and they are all the preconditioner setters there are
+    assert sorted(formed) == sorted(fn for fn in declared if "_precon" in fn)
+    assert precon_setter("lbfgs") == "mk_solver_set_precon_lbfgs" and precon_setter("lbfgs", True) == "mk_solver_set_lls_precon_bfgs"
+    assert precon_setter("diag", True) == "mk_solver_set_lls_precon" and precon_setter("device") == "mk_solver_set_precon_csr"
+
+
+def test_the_c_abi_declares_the_functions_it_declared_before():
+    assert header_functions() == sorted(ABI)
