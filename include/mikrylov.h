@@ -372,14 +372,16 @@ typedef enum {
     MK_CRAIGMR = 10,  /* pykrylov/lls/craigmr.py:51-241       */
     MK_GMRES = 11,    /* restarted GMRES(m), right preconditioned (no reference module): a square solver */
     MK_IDR = 12,      /* IDR(s), right preconditioned (no reference module): a square solver */
-    MK_PCG = 13       /* preconditioned CG, the textbook recurrence p = z + beta p (no reference module): a square solver */
+    MK_PCG = 13,      /* preconditioned CG, the textbook recurrence p = z + beta p (no reference module): a square solver */
+    MK_MSCG = 14      /* multi-shift CG: (A + sigma_k I) x_k = b for up to MK_MSCG_MAX_SHIFTS shifts in one Krylov space (no reference module): a square solver */
 } mk_solver_kind;
 
 #define MK_GMRES_MAX_RESTART 128
 #define MK_IDR_MAX_S 32
+#define MK_MSCG_MAX_SHIFTS 32
 
 typedef struct {
-    int32_t struct_size;      /* = sizeof(mk_params) */
+    int32_t struct_size;      /* = sizeof(mk_params), or sizeof(mk_params_shifts) at the head of the long block below */
     int32_t kind;             /* mk_solver_kind */
     double abstol;            /* generic.py:74 */
     double reltol;            /* generic.py:75 */
@@ -400,6 +402,17 @@ typedef struct {
     int32_t reorth;           /* MK_GMRES: 1 = classical Gram-Schmidt twice per step, 0 = once */
 } mk_params;
 
+/* The long parameter block: mk_params followed by the shifts of MK_MSCG.  mk_params itself is unchanged, so that callers
+ * compiled against it keep working; mk_solver_create tells the two apart by struct_size.  Hand it `&block.base` with
+ * block.base.struct_size = sizeof(mk_params_shifts).  Every solver kind accepts either block, only MK_MSCG reads the
+ * tail, and MK_MSCG refuses the short block (MK_ERR_ARG: it has no shifts). */
+typedef struct {
+    mk_params base;
+    int32_t nsigma;           /* number of shifts, 1 .. MK_MSCG_MAX_SHIFTS; MK_ERR_ARG otherwise */
+    int32_t sigma_reserved;   /* (padding; ignored) */
+    double sigma[MK_MSCG_MAX_SHIFTS];   /* the shifts sigma_k, k < nsigma, each finite */
+} mk_params_shifts;
+
 typedef struct {
     int32_t struct_size;
     int32_t halted;           /* the loop condition of the reference became false */
@@ -419,6 +432,9 @@ typedef struct {
                                * [3] breakdown: 0 none, 1 a zero or non-finite pivot M[k,k], 2 a zero or non-finite om */
                               /* MK_PCG: [0] the flexible flag in use, [1] breakdown: 0 none, 1 the curvature test <p, A p> > 0 failed
                                * (`definite` is 0), 2 a <r, M r> that is not positive and finite */
+                              /* MK_MSCG: [0] nsigma, [1] breakdown: 0 none, 1 the curvature test <p, A p> > 0 failed (`definite`
+                               * is 0), 2 a zero or non-finite term of a shift's zeta recurrence, or a <r, r> that is not positive
+                               * and finite, [2] frozen (converged) shifts, [3] bytes of the solver's vectors */
 } mk_result;
 
 typedef struct mk_solver mk_solver;
@@ -451,6 +467,25 @@ MK_API int mk_solver_set_idr(mk_solver *s, int32_t shadow_dim, uint64_t seed, co
  * after mk_solver_setup, MK_ERR_UNSUPPORTED on another solver kind.  mk_solver_vector: 0 = r, 1 = p (after a failed
  * curvature test: the direction that failed it; x is then untouched by that pass). */
 MK_API int mk_solver_set_pcg(mk_solver *s, int32_t flexible);
+/* MK_MSCG: multi-shift conjugate gradients (Frommer and Maass; Jegerlehner, hep-lat/9612014).  Solves (A + sigma_k I) x_k = b
+ * for the nsigma shifts of sigma[] in the long parameter block (mk_params_shifts) with ONE product per pass: CG runs on A itself (x_0 = 0, r = p = b)
+ * and every shift keeps x_k, p_k and a scalar zeta_k with r_k = zeta_k r, so that its residual norm is |zeta_k| ||r||.  Any
+ * finite shift is accepted; the caller answers for A + sigma_k I being positive definite.  It has no function of its own: it
+ * enters through the kind and the long parameter block.  mk_solver_create: MK_ERR_ARG for the short block, nsigma outside
+ * 1 .. MK_MSCG_MAX_SHIFTS or a shift that is not finite, MK_ERR_UNSUPPORTED for an operator with an exchange plan or a row
+ * block (single GPU).  No preconditioner and no initial guess (either destroys the collinearity of the residuals): every
+ * preconditioner setter answers MK_ERR_UNSUPPORTED, mk_solver_setup with a guess MK_ERR_ARG.  r, p, q and 2 nsigma vectors
+ * are allocated at the first set-up.  threshold = max(abstol, reltol ||b||); after the updates of a pass a shift with
+ * |zeta_k| ||r|| <= threshold is frozen: x_k has that pass's update, and from then on neither its vectors nor its scalars
+ * are touched.  The loop ends when no shift is active or nMatvec >= matvec_max.  mk_params.check_curvature as in MK_CG: a
+ * <p, A p> that is not positive ends the run with nothing updated in that pass (breakdown 1); so does a zero or non-finite
+ * term of a zeta recurrence (breakdown 2), every x_k then being its last iterate.
+ * mk_solver_x = x_0.  mk_solver_vector: 0 = r, 1 = p (base recurrence), 2 + k = x_k, 2 + nsigma + k = p_k,
+ * 2 + 2 nsigma = the per-shift record, len = 3 nsigma: entries 3 k, 3 k + 1, 3 k + 2 hold zeta_k, |zeta_k| ||r|| and the
+ * pass at which shift k froze (-1: still active); any other index MK_ERR_ARG.  mk_solver_history = ||r|| of the base
+ * recurrence, ||b|| first; mk_solver_history2 = per pass the largest |zeta_k| ||r|| over the shifts that entered the pass
+ * active (||b|| first).  mk_result: converged = every shift frozen, residNorm = the largest per-shift residual norm, aux as
+ * listed at mk_result. */
 /* Several GPUs: mark `A` as THIS rank's block of consecutive rows of a taller m x n operator (its columns are global
  * and unlocalized; no mk_csr_set_exchange).  The least-squares solvers then keep every m-space vector (rhs, u, r;
  * x of CRAIG-MR) sliced like the rows and every n-space vector (v, w, x) whole on every rank: `A * v` needs no

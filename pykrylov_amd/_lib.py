@@ -23,6 +23,8 @@ MK_GMRES_MAX_RESTART = 128
 MK_IDR = 12
 MK_IDR_MAX_S = 32
 MK_PCG = 13
+MK_MSCG = 14
+MK_MSCG_MAX_SHIFTS = 32
 
 
 class MkParams(ctypes.Structure):
@@ -31,6 +33,11 @@ class MkParams(ctypes.Structure):
                 ("rtol", c_f64), ("etol", c_f64), ("itnlim", c_i64), ("window", c_i32), ("spmv_event_stride", c_i32),
                 ("damp", c_f64), ("atol", c_f64), ("btol", c_f64), ("conlim", c_f64),
                 ("restart", c_i32), ("reorth", c_i32)]
+
+
+class MkParamsShifts(ctypes.Structure):
+    "mk_params_shifts (include/mikrylov.h): mk_params followed by the shifts of MK_MSCG; mk_solver_create takes `.base`."
+    _fields_ = [("base", MkParams), ("nsigma", c_i32), ("sigma_reserved", c_i32), ("sigma", c_f64 * MK_MSCG_MAX_SHIFTS)]
 
 
 class MkRowOp(ctypes.Structure):

@@ -147,6 +147,8 @@ struct mk_solver {
     // result on the device
     int apply_slot(const MkPrecon &slot, const double *in_dev, double *out_dev, bool force, const double *need_pos = nullptr);
     mk_params prm{};
+    int nsigma = 0;                              // MK_MSCG: the shifts of the long parameter block (mk_params_shifts)
+    double sigma[MK_MSCG_MAX_SHIFTS] = {};
     int64_t n = 0;        // local rows = length of every solver vector
     int64_t nx = 0;       // length of vectors that feed an SpMV (n + halo)
     hipStream_t stream = nullptr;
@@ -185,6 +187,7 @@ struct mk_solver {
     virtual int finish(mk_result *res) = 0;
     virtual const double *x() const = 0;
     virtual const double *vector(int) const { return nullptr; }
+    virtual int64_t vector_len(int) const { return n; }   // entries of `vector(i)` (multi-shift CG's record is not a solver vector)
     virtual bool takes_precon() const { return false; }
     virtual bool is_fused() const { return false; }   // CG on a format-9 matrix: the x / p update rides in the next product kernel
     // work a loop defers beyond its passes (CG: the x update over a ring of directions): `drain` enqueues what is applicable at
@@ -225,6 +228,7 @@ mk_solver *mk_make_lls(int kind);
 mk_solver *mk_make_gmres();
 mk_solver *mk_make_idr();
 mk_solver *mk_make_pcg();
+mk_solver *mk_make_mscg();
 
 #ifdef __HIPCC__
 // ------------------------------------------------------------------ small shared kernels

@@ -1,6 +1,8 @@
 // mk_solver.hip -- generic driver of the device-resident solver loops + C ABI dispatch.
 #include "mk_solver.h"
 
+#include <cmath>
+
 int mk_solver::init_common(const mk_csr *A_, const mk_params *p) {
     A = A_;
     A->dependents += 1;              // (borrowed for the solver's lifetime: destroying A meanwhile is deferred)
@@ -290,7 +292,10 @@ void mk_solver::fill_result(mk_result *res) const {
 extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_solver **out) {
     MK_REQUIRE_INIT();
     MK_ARG(A && params && out);
-    MK_ARG(params->struct_size == (int32_t)sizeof(mk_params));
+    // the short block, or the long one whose tail carries the shifts of MK_MSCG (every kind takes either)
+    const mk_params_shifts *shifts = nullptr;
+    if (params->struct_size == (int32_t)sizeof(mk_params_shifts)) shifts = reinterpret_cast<const mk_params_shifts *>(params);
+    else MK_ARG(params->struct_size == (int32_t)sizeof(mk_params));
     mk_solver *s = nullptr;
     switch (params->kind) {
         case MK_CG: s = mk_make_cg(); break;
@@ -324,11 +329,31 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
                                "plan or a row block); PCG is single-GPU");
             s = mk_make_pcg();
             break;
+        case MK_MSCG:
+            if (!shifts)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: multi-shift CG takes its shifts in the long parameter block "
+                               "(struct_size = sizeof(mk_params_shifts))");
+            if (shifts->nsigma < 1 || shifts->nsigma > MK_MSCG_MAX_SHIFTS)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: multi-shift CG nsigma = %d, must be 1 .. %d", (int)shifts->nsigma,
+                               MK_MSCG_MAX_SHIFTS);
+            for (int k = 0; k < shifts->nsigma; ++k)
+                if (!std::isfinite(shifts->sigma[k]))
+                    return mk_fail(MK_ERR_ARG, "mk_solver_create: multi-shift CG sigma[%d] is not finite", k);
+            if (A->ex.mode >= 0 || A->row_block)
+                return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: the operator is row-partitioned (it carries an exchange "
+                               "plan or a row block); multi-shift CG is single-GPU");
+            s = mk_make_mscg();
+            break;
         default: break;
     }
     if (!s) return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: solver kind %d is not available", params->kind);
-    // (before the partial-sum counts are sized for the format in use; PCG's product kernels are CG's, mk_cg_epi.h)
-    mk_csr_march_pref(A, params->kind == MK_CG || params->kind == MK_PCG ? 1 : 0);
+    // (before the partial-sum counts are sized for the format in use; PCG's and multi-shift CG's product kernels are CG's,
+    //  mk_cg_epi.h)
+    mk_csr_march_pref(A, params->kind == MK_CG || params->kind == MK_PCG || params->kind == MK_MSCG ? 1 : 0);
+    if (shifts && params->kind == MK_MSCG) {
+        s->nsigma = shifts->nsigma;
+        memcpy(s->sigma, shifts->sigma, sizeof(double) * (size_t)shifts->nsigma);
+    }
     int rc = s->init_common(A, params);
     if (rc != MK_OK) {
         delete s;
@@ -573,7 +598,7 @@ extern "C" int mk_solver_vector(const mk_solver *s, int index, const double **v_
     const double *v = s->vector(index);
     if (!v) return mk_fail(MK_ERR_ARG, "mk_solver_vector: index %d is not defined for this solver", index);
     *v_dev = v;
-    if (len) *len = s->n;
+    if (len) *len = s->vector_len(index);
     return MK_OK;
 }
 

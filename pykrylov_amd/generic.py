@@ -239,11 +239,14 @@ class DeviceRun(object):
         # nrows(A) entries.  `sides`: their M and N, a pair of `resolve_precon` payloads.  `placement_draws`: see _draws().
         # `idr`: (s, seed, shadow) of mk_solver_set_idr, the shadow vectors None or an (s, n) fp64 array.
         # `pcg`: (flexible,) of mk_solver_set_pcg.
+        # `shifts`: the shifts of multi-shift CG; they travel in the long parameter block (mk_params_shifts), whose head
+        # is the mk_params every kind takes.
         transpose = params.pop('transpose', None)
         sides = params.pop('sides', None)
         draws = params.pop('placement_draws', None)
         self.idr = params.pop('idr', None)
         self.pcg = params.pop('pcg', None)
+        shifts = params.pop('shifts', None)
         self._d_shadow = None
         if draws is not None:
             self.placement_draws = int(draws)
@@ -260,8 +263,18 @@ class DeviceRun(object):
             _lib.DeviceArray.from_numpy(as_f64_vector(guess, n, 'guess')))
         if self.d_rhs.n != n or (self.d_guess is not None and self.d_guess.n != n):
             raise ValueError('rhs / guess must have %d entries' % n)
-        p = _lib.MkParams()
-        p.struct_size = ctypes.sizeof(_lib.MkParams)
+        if shifts is None:
+            p = _lib.MkParams()
+            p.struct_size = ctypes.sizeof(_lib.MkParams)
+        else:
+            if len(shifts) > _lib.MK_MSCG_MAX_SHIFTS:
+                raise ValueError('at most %d shifts, got %d' % (_lib.MK_MSCG_MAX_SHIFTS, len(shifts)))
+            block = _lib.MkParamsShifts()
+            block.nsigma = len(shifts)
+            for k, v in enumerate(shifts):
+                block.sigma[k] = float(v)
+            p = block.base                                   # (a view: it writes into the block and keeps it alive)
+            p.struct_size = ctypes.sizeof(_lib.MkParamsShifts)
         p.kind = kind
         for k, v in params.items():
             setattr(p, k, v)

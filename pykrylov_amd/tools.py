@@ -177,7 +177,7 @@ def _checked_int(what, name, v, lo, hi, must=None):
 
 class DevicePreconditioner(LinearOperator):
     """What the device preconditioner objects of this module share: a handle of libmikrylov.so whose entry points are
-    ``mk_<_abi>_apply`` / ``_info`` / ``_destroy`` (DESIGN.md 3.13).  ``self * v`` applies the object to a NumPy vector,
+    ``mk_<_abi>_apply`` / ``_info`` / ``_destroy`` (DESIGN.md 3.14).  ``self * v`` applies the object to a NumPy vector,
     `apply_device` to DeviceArray vectors; a solver given it as ``precon=`` (``M=`` / ``N=``) applies it on the device
     (``mk_solver_set_precon_<route>``, `generic.PRECON_SETTERS`).  `free()` releases this object's reference; a solver
     that still applies the object keeps it alive.  A kind gives the class attributes below, creates its handle and ends
