@@ -373,15 +373,17 @@ typedef enum {
     MK_GMRES = 11,    /* restarted GMRES(m), right preconditioned (no reference module): a square solver */
     MK_IDR = 12,      /* IDR(s), right preconditioned (no reference module): a square solver */
     MK_PCG = 13,      /* preconditioned CG, the textbook recurrence p = z + beta p (no reference module): a square solver */
-    MK_MSCG = 14      /* multi-shift CG: (A + sigma_k I) x_k = b for up to MK_MSCG_MAX_SHIFTS shifts in one Krylov space (no reference module): a square solver */
+    MK_MSCG = 14,     /* multi-shift CG: (A + sigma_k I) x_k = b for up to MK_MSCG_MAX_SHIFTS shifts in one Krylov space (no reference module): a square solver */
+    MK_TRLAN = 15     /* thick-restart Lanczos (Wu and Simon): the nev smallest or largest eigenpairs of a symmetric operator (no reference module); not a solver of A x = b */
 } mk_solver_kind;
 
 #define MK_GMRES_MAX_RESTART 128
 #define MK_IDR_MAX_S 32
 #define MK_MSCG_MAX_SHIFTS 32
+#define MK_TRLAN_MAX_NCV 128
 
 typedef struct {
-    int32_t struct_size;      /* = sizeof(mk_params), or sizeof(mk_params_shifts) at the head of the long block below */
+    int32_t struct_size;      /* = sizeof(mk_params), or sizeof(mk_params_shifts) / sizeof(mk_params_eig) at the head of a long block below */
     int32_t kind;             /* mk_solver_kind */
     double abstol;            /* generic.py:74 */
     double reltol;            /* generic.py:75 */
@@ -413,6 +415,19 @@ typedef struct {
     double sigma[MK_MSCG_MAX_SHIFTS];   /* the shifts sigma_k, k < nsigma, each finite */
 } mk_params_shifts;
 
+/* The second long parameter block: mk_params followed by what MK_TRLAN asks for.  It is told apart by struct_size like the
+ * first: hand mk_solver_create `&block.base` with block.base.struct_size = sizeof(mk_params_eig).  Every solver kind accepts
+ * it, only MK_TRLAN reads the tail, and MK_TRLAN refuses the other two blocks (MK_ERR_ARG).  MK_ERR_ARG unless
+ * 1 <= nev < ncv <= min(n, MK_TRLAN_MAX_NCV) and, for a keep that is not 0, nev <= keep < ncv. */
+typedef struct {
+    mk_params base;
+    int32_t nev;              /* eigenpairs wanted */
+    int32_t ncv;              /* basis vectors per cycle */
+    int32_t which;            /* 0 = the smallest ('SA'), 1 = the largest ('LA'); MK_ERR_ARG otherwise */
+    int32_t keep;             /* Ritz vectors kept at a restart; 0 = automatic: min(nev + (ncv - nev) / 2, ncv - 1) */
+    uint64_t seed;            /* of the hashed start vector (mk_solver_setup with a NULL start) */
+} mk_params_eig;
+
 typedef struct {
     int32_t struct_size;
     int32_t halted;           /* the loop condition of the reference became false */
@@ -435,6 +450,10 @@ typedef struct {
                               /* MK_MSCG: [0] nsigma, [1] breakdown: 0 none, 1 the curvature test <p, A p> > 0 failed (`definite`
                                * is 0), 2 a zero or non-finite term of a shift's zeta recurrence, or a <r, r> that is not positive
                                * and finite, [2] frozen (converged) shifts, [3] bytes of the solver's vectors */
+                              /* MK_TRLAN: [0] cycles, [1] the ncv in use, [2] the keep in use, [3] bytes of the basis allocation,
+                               * [4] wanted pairs whose estimate met the threshold in the last cycle, [5] breakdown (0 / 1),
+                               * [6] Jacobi sweeps of the last cycle's small eigenproblem, [7] milliseconds the device spent in the
+                               * last restart's rotation (0 before the first restart) */
 } mk_result;
 
 typedef struct mk_solver mk_solver;
@@ -486,6 +505,34 @@ MK_API int mk_solver_set_pcg(mk_solver *s, int32_t flexible);
  * recurrence, ||b|| first; mk_solver_history2 = per pass the largest |zeta_k| ||r|| over the shifts that entered the pass
  * active (||b|| first).  mk_result: converged = every shift frozen, residNorm = the largest per-shift residual norm, aux as
  * listed at mk_result. */
+/* MK_TRLAN: thick-restart Lanczos (Wu and Simon) for the nev smallest (which = 0) or largest (1) eigenvalues of a symmetric
+ * operator and their eigenvectors; the caller answers for the symmetry.  It has no function of its own: it enters through
+ * the kind and the long parameter block mk_params_eig.  mk_solver_create: MK_ERR_ARG for the short block, the shifts block or
+ * a tail outside the ranges listed at mk_params_eig; MK_ERR_UNSUPPORTED for an operator with an exchange plan or a row
+ * block (single GPU).  Every preconditioner setter answers MK_ERR_UNSUPPORTED.
+ * mk_solver_setup(s, start_dev, NULL): the start vector, n doubles, borrowed for the call -- for this kind only it may be
+ * NULL, which selects the hashed vector mk_cell_field(i, seed) - 1.0 of mk_csr_lanczos.  A guess is MK_ERR_ARG; so are
+ * matvec_max < ncv and a start vector whose norm is not positive and finite.  The basis -- ncv + 1 columns and
+ * 16 (ceil(keep / 16) - 1) spare ones, each of n rounded up to even plus 2 doubles -- is allocated at the first set-up
+ * (MK_ERR_HIP with the sizes if it does not fit).
+ * One pass of mk_solver_iterate is one whole cycle: Lanczos steps with full orthogonalisation (classical Gram-Schmidt twice)
+ * until the basis is full, without a transfer to the host; then one download of the step scalars, the eigenproblem of the
+ * ncv x ncv projected matrix on the host (cyclic Jacobi), one upload of the rotation coefficients and the rotation
+ * V[:, :keep] = V S[:, kept] on the device.  est_i = |beta_last S[last, i]| estimates the residual norm of Ritz pair i;
+ * threshold = max(abstol, reltol anorm), anorm the largest |Ritz value| seen so far.  The run ends when the nev wanted pairs
+ * all have est <= threshold (converged), when a step's beta is not > 2^-26 tmax (breakdown: the basis spans an invariant
+ * subspace, every Ritz pair is exact; converged iff it holds at least nev vectors), or when the next cycle's ncv - keep
+ * products would exceed matvec_max, which is therefore never exceeded.
+ * mk_solver_x = the first eigenvector; mk_solver_vector(i), i < nev: eigenvector i in ascending order of the eigenvalues
+ * (after a breakdown with fewer than nev basis vectors only that many are defined); mk_solver_vector(nev) = the record,
+ * len = 3 nev: entries 3 i, 3 i + 1, 3 i + 2 hold theta_i, est_i and the cycle (from 1) at which the pair in that place of
+ * the wanted order first met the threshold (-1: never); pairs that do not exist hold NaN, NaN, -1.  mk_solver_history = one
+ * entry per cycle, the largest estimate among the wanted pairs; mk_solver_history2 = per cycle the milliseconds of its host
+ * part (the small eigenproblem, the stop tests and the enqueueing of the rotation: a measurement).  mk_params.window != 0
+ * composes the rotation of GmOpCombine launches instead (one output column at a time, keep spare columns; the same bits:
+ * the comparison tools/trlan_bench.py makes).  mk_result: itn = Lanczos steps, nMatvec = products,
+ * converged and threshold as above, residNorm = the last history entry, residNorm0 = ||start||, aux as listed at
+ * mk_result. */
 /* Several GPUs: mark `A` as THIS rank's block of consecutive rows of a taller m x n operator (its columns are global
  * and unlocalized; no mk_csr_set_exchange).  The least-squares solvers then keep every m-space vector (rhs, u, r;
  * x of CRAIG-MR) sliced like the rows and every n-space vector (v, w, x) whole on every rank: `A * v` needs no

@@ -19,6 +19,7 @@ from .gmres import GMRES                                                        
 from .idr import IDR                                                                            # noqa: F401
 from .pcg import PCG                                                                            # noqa: F401
 from .mscg import ShiftedCG                                                                     # noqa: F401
+from .trlan import ThickRestartLanczos, eigsh                                                   # noqa: F401
 from .minres import Minres                                                                      # noqa: F401
 from .symmlq import Symmlq                                                                      # noqa: F401
 from .lbfgs import InverseLBFGSOperator, LBFGSOperator, CompactLBFGSOperator                    # noqa: F401

@@ -25,6 +25,8 @@ MK_IDR_MAX_S = 32
 MK_PCG = 13
 MK_MSCG = 14
 MK_MSCG_MAX_SHIFTS = 32
+MK_TRLAN = 15
+MK_TRLAN_MAX_NCV = 128
 
 
 class MkParams(ctypes.Structure):
@@ -38,6 +40,13 @@ class MkParams(ctypes.Structure):
 class MkParamsShifts(ctypes.Structure):
     "mk_params_shifts (include/mikrylov.h): mk_params followed by the shifts of MK_MSCG; mk_solver_create takes `.base`."
     _fields_ = [("base", MkParams), ("nsigma", c_i32), ("sigma_reserved", c_i32), ("sigma", c_f64 * MK_MSCG_MAX_SHIFTS)]
+
+
+class MkParamsEig(ctypes.Structure):
+    """mk_params_eig (include/mikrylov.h): mk_params followed by what MK_TRLAN asks for (`which`: 0 = smallest, 1 = largest;
+    `keep` 0 = automatic); mk_solver_create takes `.base`."""
+    _fields_ = [("base", MkParams), ("nev", c_i32), ("ncv", c_i32), ("which", c_i32), ("keep", c_i32),
+                ("seed", ctypes.c_uint64)]
 
 
 class MkRowOp(ctypes.Structure):

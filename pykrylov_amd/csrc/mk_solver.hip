@@ -1,6 +1,7 @@
 // mk_solver.hip -- generic driver of the device-resident solver loops + C ABI dispatch.
 #include "mk_solver.h"
 
+#include <algorithm>
 #include <cmath>
 
 int mk_solver::init_common(const mk_csr *A_, const mk_params *p) {
@@ -292,9 +293,12 @@ void mk_solver::fill_result(mk_result *res) const {
 extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_solver **out) {
     MK_REQUIRE_INIT();
     MK_ARG(A && params && out);
-    // the short block, or the long one whose tail carries the shifts of MK_MSCG (every kind takes either)
+    // the short block, or a long one whose tail carries the shifts of MK_MSCG or the eigenproblem of MK_TRLAN (every kind
+    // takes any of them)
     const mk_params_shifts *shifts = nullptr;
+    const mk_params_eig *eig = nullptr;
     if (params->struct_size == (int32_t)sizeof(mk_params_shifts)) shifts = reinterpret_cast<const mk_params_shifts *>(params);
+    else if (params->struct_size == (int32_t)sizeof(mk_params_eig)) eig = reinterpret_cast<const mk_params_eig *>(params);
     else MK_ARG(params->struct_size == (int32_t)sizeof(mk_params));
     mk_solver *s = nullptr;
     switch (params->kind) {
@@ -344,6 +348,31 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
                                "plan or a row block); multi-shift CG is single-GPU");
             s = mk_make_mscg();
             break;
+        case MK_TRLAN: {
+            if (!eig)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: thick-restart Lanczos takes nev, ncv, which, keep and seed in its "
+                               "long parameter block (struct_size = sizeof(mk_params_eig))");
+            if (A->ex.mode >= 0 || A->row_block)
+                return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: the operator is row-partitioned (it carries an exchange "
+                               "plan or a row block); thick-restart Lanczos is single-GPU");
+            const int64_t top = A->nrows < MK_TRLAN_MAX_NCV ? A->nrows : MK_TRLAN_MAX_NCV;
+            if (!(1 <= eig->nev && eig->nev < eig->ncv && (int64_t)eig->ncv <= top))
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: thick-restart Lanczos nev = %d, ncv = %d, must be 1 <= nev < ncv <= "
+                               "min(n, %d) = %lld", (int)eig->nev, (int)eig->ncv, MK_TRLAN_MAX_NCV, (long long)top);
+            if (eig->keep != 0 && !(eig->nev <= eig->keep && eig->keep < eig->ncv))
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: thick-restart Lanczos keep = %d, must be 0 (automatic) or nev = %d "
+                               "<= keep < ncv = %d", (int)eig->keep, (int)eig->nev, (int)eig->ncv);
+            if (eig->which != 0 && eig->which != 1)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: thick-restart Lanczos which = %d, must be 0 (smallest) or 1 "
+                               "(largest)", (int)eig->which);
+            s = mk_make_trlan();
+            s->eig_nev = eig->nev;
+            s->eig_ncv = eig->ncv;
+            s->eig_which = eig->which;
+            s->eig_keep = eig->keep ? eig->keep : std::min(eig->nev + (eig->ncv - eig->nev) / 2, eig->ncv - 1);
+            s->eig_seed = eig->seed;
+            break;
+        }
         default: break;
     }
     if (!s) return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: solver kind %d is not available", params->kind);
@@ -516,7 +545,7 @@ extern "C" int mk_solver_destroy(mk_solver *s) {
 }
 
 extern "C" int mk_solver_setup(mk_solver *s, const double *rhs, const double *guess) {
-    MK_ARG(s && rhs);
+    MK_ARG(s && (rhs || s->prm.kind == MK_TRLAN));            // (thick-restart Lanczos: no start vector selects the hashed one)
     MK_ARG(MK_ALIGNED16(rhs) && MK_ALIGNED16(guess));        // borrowed vectors are read in 16-byte pairs
     s->q = 0;
     s->it = 0;

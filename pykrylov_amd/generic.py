@@ -241,12 +241,15 @@ class DeviceRun(object):
         # `pcg`: (flexible,) of mk_solver_set_pcg.
         # `shifts`: the shifts of multi-shift CG; they travel in the long parameter block (mk_params_shifts), whose head
         # is the mk_params every kind takes.
+        # `eig`: (nev, ncv, which, keep, seed) of thick-restart Lanczos, in the second long block (mk_params_eig).  For that
+        # kind `rhs` is the start vector and may be None (the hashed one).
         transpose = params.pop('transpose', None)
         sides = params.pop('sides', None)
         draws = params.pop('placement_draws', None)
         self.idr = params.pop('idr', None)
         self.pcg = params.pop('pcg', None)
         shifts = params.pop('shifts', None)
+        eig = params.pop('eig', None)
         self._d_shadow = None
         if draws is not None:
             self.placement_draws = int(draws)
@@ -256,14 +259,22 @@ class DeviceRun(object):
         self.n_x = n if (transpose is None or kind == _lib.MK_CRAIGMR) else op.shape[1]
         # rhs / guess: host arrays (copied to HBM) or DeviceArray objects already resident there
         self._borrowed = [b for b in (rhs, guess) if isinstance(b, _lib.DeviceArray)]
-        self.d_rhs = rhs if isinstance(rhs, _lib.DeviceArray) else \
-            _lib.DeviceArray.from_numpy(as_f64_vector(rhs, n, 'rhs'))
+        if rhs is None and kind == _lib.MK_TRLAN:
+            self.d_rhs = None
+        else:
+            self.d_rhs = rhs if isinstance(rhs, _lib.DeviceArray) else \
+                _lib.DeviceArray.from_numpy(as_f64_vector(rhs, n, 'rhs'))
         self.d_guess = None if guess is None else (
             guess if isinstance(guess, _lib.DeviceArray) else
             _lib.DeviceArray.from_numpy(as_f64_vector(guess, n, 'guess')))
-        if self.d_rhs.n != n or (self.d_guess is not None and self.d_guess.n != n):
+        if (self.d_rhs is not None and self.d_rhs.n != n) or (self.d_guess is not None and self.d_guess.n != n):
             raise ValueError('rhs / guess must have %d entries' % n)
-        if shifts is None:
+        if eig is not None:
+            block = _lib.MkParamsEig()
+            block.nev, block.ncv, block.which, block.keep, block.seed = [int(v) for v in eig]
+            p = block.base                                   # (a view: it writes into the block and keeps it alive)
+            p.struct_size = ctypes.sizeof(_lib.MkParamsEig)
+        elif shifts is None:
             p = _lib.MkParams()
             p.struct_size = ctypes.sizeof(_lib.MkParams)
         else:
@@ -410,7 +421,7 @@ class DeviceRun(object):
 
     def _timed_passes(self, handle, warm=4, passes=12):
         g = None if self.d_guess is None else self.d_guess.ptr
-        self._check(self.lib.mk_solver_setup(handle, self.d_rhs.ptr, g))
+        self._check(self.lib.mk_solver_setup(handle, None if self.d_rhs is None else self.d_rhs.ptr, g))
         done = ctypes.c_int64(0)
         self._check(self.lib.mk_solver_iterate(handle, warm, ctypes.byref(done)))
         self._check(self.lib.mk_sync())
@@ -461,7 +472,7 @@ class DeviceRun(object):
         draws = self._draws()
         if draws > 1:
             self._draw_placement(draws)
-        self._check(self.lib.mk_solver_setup(self.handle, self.d_rhs.ptr,
+        self._check(self.lib.mk_solver_setup(self.handle, None if self.d_rhs is None else self.d_rhs.ptr,
                                              None if self.d_guess is None else self.d_guess.ptr))
         self._setup_done = True
 
