@@ -374,13 +374,15 @@ typedef enum {
     MK_IDR = 12,      /* IDR(s), right preconditioned (no reference module): a square solver */
     MK_PCG = 13,      /* preconditioned CG, the textbook recurrence p = z + beta p (no reference module): a square solver */
     MK_MSCG = 14,     /* multi-shift CG: (A + sigma_k I) x_k = b for up to MK_MSCG_MAX_SHIFTS shifts in one Krylov space (no reference module): a square solver */
-    MK_TRLAN = 15     /* thick-restart Lanczos (Wu and Simon): the nev smallest or largest eigenpairs of a symmetric operator (no reference module); not a solver of A x = b */
+    MK_TRLAN = 15,    /* thick-restart Lanczos (Wu and Simon): the nev smallest or largest eigenpairs of a symmetric operator (no reference module); not a solver of A x = b */
+    MK_LOBPCG = 16    /* LOBPCG (Knyazev): a block, preconditioned eigensolver with soft locking for the nev smallest or largest eigenpairs of a symmetric operator (no reference module); not a solver of A x = b */
 } mk_solver_kind;
 
 #define MK_GMRES_MAX_RESTART 128
 #define MK_IDR_MAX_S 32
 #define MK_MSCG_MAX_SHIFTS 32
 #define MK_TRLAN_MAX_NCV 128
+#define MK_LOBPCG_MAX_BLOCK 16
 
 typedef struct {
     int32_t struct_size;      /* = sizeof(mk_params), or sizeof(mk_params_shifts) / sizeof(mk_params_eig) at the head of a long block below */
@@ -415,17 +417,19 @@ typedef struct {
     double sigma[MK_MSCG_MAX_SHIFTS];   /* the shifts sigma_k, k < nsigma, each finite */
 } mk_params_shifts;
 
-/* The second long parameter block: mk_params followed by what MK_TRLAN asks for.  It is told apart by struct_size like the
- * first: hand mk_solver_create `&block.base` with block.base.struct_size = sizeof(mk_params_eig).  Every solver kind accepts
- * it, only MK_TRLAN reads the tail, and MK_TRLAN refuses the other two blocks (MK_ERR_ARG).  MK_ERR_ARG unless
- * 1 <= nev < ncv <= min(n, MK_TRLAN_MAX_NCV) and, for a keep that is not 0, nev <= keep < ncv. */
+/* The second long parameter block: mk_params followed by what the eigensolvers MK_TRLAN and MK_LOBPCG ask for.  It is told
+ * apart by struct_size like the first: hand mk_solver_create `&block.base` with block.base.struct_size =
+ * sizeof(mk_params_eig).  Every solver kind accepts it, only MK_TRLAN and MK_LOBPCG read the tail, and both refuse the other
+ * two blocks (MK_ERR_ARG).  MK_TRLAN: MK_ERR_ARG unless 1 <= nev < ncv <= min(n, MK_TRLAN_MAX_NCV) and, for a keep that is
+ * not 0, nev <= keep < ncv.  MK_LOBPCG: `ncv` carries the block size nb, MK_ERR_ARG unless
+ * 1 <= nev <= nb <= min(MK_LOBPCG_MAX_BLOCK, n / 3) and keep == 0. */
 typedef struct {
     mk_params base;
     int32_t nev;              /* eigenpairs wanted */
-    int32_t ncv;              /* basis vectors per cycle */
+    int32_t ncv;              /* MK_TRLAN: basis vectors per cycle; MK_LOBPCG: the block size nb */
     int32_t which;            /* 0 = the smallest ('SA'), 1 = the largest ('LA'); MK_ERR_ARG otherwise */
-    int32_t keep;             /* Ritz vectors kept at a restart; 0 = automatic: min(nev + (ncv - nev) / 2, ncv - 1) */
-    uint64_t seed;            /* of the hashed start vector (mk_solver_setup with a NULL start) */
+    int32_t keep;             /* MK_TRLAN: Ritz vectors kept at a restart; 0 = automatic: min(nev + (ncv - nev) / 2, ncv - 1); MK_LOBPCG: must be 0 */
+    uint64_t seed;            /* of the hashed start vector (mk_solver_setup with a NULL start); MK_LOBPCG: column j takes seed + j */
 } mk_params_eig;
 
 typedef struct {
@@ -454,6 +458,10 @@ typedef struct {
                                * [4] wanted pairs whose estimate met the threshold in the last cycle, [5] breakdown (0 / 1),
                                * [6] Jacobi sweeps of the last cycle's small eigenproblem, [7] milliseconds the device spent in the
                                * last restart's rotation (0 before the first restart) */
+                              /* MK_LOBPCG: [0] iterations, [1] the block size nb, [2] active columns of the last iteration,
+                               * [3] bytes of the workspace allocation, [4] wanted pairs whose residual met the threshold,
+                               * [5] breakdown (0 / 1), [6] Jacobi sweeps of the last small eigenproblem, [7] restarts (small
+                               * problems solved again without P, and re-activations of a fully locked block) */
 } mk_result;
 
 typedef struct mk_solver mk_solver;
@@ -533,6 +541,40 @@ MK_API int mk_solver_set_pcg(mk_solver *s, int32_t flexible);
  * the comparison tools/trlan_bench.py makes).  mk_result: itn = Lanczos steps, nMatvec = products,
  * converged and threshold as above, residNorm = the last history entry, residNorm0 = ||start||, aux as listed at
  * mk_result. */
+/* MK_LOBPCG: the locally optimal block preconditioned conjugate gradient method (Knyazev 2001) for the nev smallest
+ * (which = 0) or largest (1) eigenvalues of a symmetric operator, counted with their multiplicity, and their eigenvectors;
+ * the caller answers for the symmetry.  It has no function of its own: it enters through the kind and mk_params_eig, whose
+ * `ncv` carries the block size nb.  mk_solver_create: MK_ERR_ARG for the short block, the shifts block or a tail outside the
+ * ranges listed at mk_params_eig; MK_ERR_UNSUPPORTED for an operator with an exchange plan or a row block (single GPU).
+ * Every preconditioner setter of a square solver works: W_j = precon R_j per active column.  The preconditioner approximates
+ * the inverse of A, which steers towards the smallest eigenvalues; the caller keeps it away from which = 1.
+ * mk_solver_setup(s, start_dev, NULL): the start block, nb n doubles, column after column, borrowed for the call -- or NULL:
+ * column j is the hashed vector mk_cell_field(i, seed + j) - 1.0.  A guess is MK_ERR_ARG; so is matvec_max < nb.  The
+ * workspace -- 13 nb columns of n rounded up to even plus 2 doubles (X, W, P and their products twice over, and R), then the
+ * partial sums of the Gram kernel -- is one allocation made at the first set-up (MK_ERR_HIP with the sizes if it does not
+ * fit).  Set-up forms A X (nb products), solves the first small problem and rotates X.
+ * One pass of mk_solver_iterate is one iteration: the host picks the active columns (soft locking: the columns whose residual
+ * norm exceeds the threshold; a locked column stays locked), W_j = precon R_j, W <- W - X (X'W) twice, scaled to unit norm,
+ * A W (one product per active column), the Gram matrices S'S and S'(A S) of S = [X, W, P] by the tall-skinny Gram kernel
+ * (tiles on and above the diagonal), one download of both, the small problem on the host (diagonal scaling, a Cholesky factor
+ * with the pivot test v > 2^-26, cyclic Jacobi), one upload of the coefficients, the rotations X <- S C, A X <- (A S) C,
+ * P and A P likewise from the W and P rows of C, the residuals R = A X - X diag(theta) with their norms in one kernel, and
+ * one download of the nb norms.  A pivot that fails the test drops P and solves the leading problem again (a restart); a
+ * second failure ends the run (breakdown: x is the last iterate).  threshold = max(abstol, reltol anorm), anorm the largest
+ * |Ritz value| of any small problem so far.  The run ends when the first nev residual norms are all <= threshold
+ * (converged), at a breakdown, or when the active products of the next iteration would exceed matvec_max, which is
+ * therefore never exceeded.
+ * mk_solver_x = the first eigenvector; mk_solver_vector(i), i < nev: eigenvector i in ascending order of the eigenvalues;
+ * mk_solver_vector(nev) = the record, len = 3 nev: theta_i, the residual norm ||A x_i - theta_i x_i|| from the loop's own
+ * A X, and the iteration (from 0: the start block's own Ritz pairs) at which the pair first met the threshold (-1: never).
+ * mk_solver_history = the largest of the first nev residual norms, once for the start block and once per iteration;
+ * mk_solver_history2 = the milliseconds of each iteration's host part.  mk_result: itn = iterations, nMatvec = products,
+ * residNorm = the last history entry, Anorm = anorm, aux as listed at mk_result.
+ * Test hooks of the kind (no function of their own): mk_params.window = 4 or 8 forces the Gram kernel's 4 x 4 or 8 x 8 tile,
+ * 1 composes the Gram matrices of GmOpMultiDot launches (the same bits: what tools/lobpcg_bench.py times the kernel
+ * against); mk_params.restart = 1 makes the solver a probe of the Gram kernel alone: `ncv` = m, 1 .. 48, columns of n
+ * doubles in the start block, set-up forms U'U (the entries on and above the diagonal, mirrored), ends the run, and
+ * mk_solver_vector(0) returns the m x m result; aux[7] = the milliseconds of the Gram launches. */
 /* Several GPUs: mark `A` as THIS rank's block of consecutive rows of a taller m x n operator (its columns are global
  * and unlocalized; no mk_csr_set_exchange).  The least-squares solvers then keep every m-space vector (rhs, u, r;
  * x of CRAIG-MR) sliced like the rows and every n-space vector (v, w, x) whole on every rank: `A * v` needs no

@@ -20,6 +20,7 @@ from .idr import IDR                                                            
 from .pcg import PCG                                                                            # noqa: F401
 from .mscg import ShiftedCG                                                                     # noqa: F401
 from .trlan import ThickRestartLanczos, eigsh                                                   # noqa: F401
+from .lobpcg import LOBPCG, lobpcg                                                              # noqa: F401
 from .minres import Minres                                                                      # noqa: F401
 from .symmlq import Symmlq                                                                      # noqa: F401
 from .lbfgs import InverseLBFGSOperator, LBFGSOperator, CompactLBFGSOperator                    # noqa: F401

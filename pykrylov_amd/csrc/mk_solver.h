@@ -149,7 +149,7 @@ struct mk_solver {
     mk_params prm{};
     int nsigma = 0;                              // MK_MSCG: the shifts of the long parameter block (mk_params_shifts)
     double sigma[MK_MSCG_MAX_SHIFTS] = {};
-    int eig_nev = 0, eig_ncv = 0, eig_which = 0, eig_keep = 0;   // MK_TRLAN: the tail of its long parameter block (mk_params_eig)
+    int eig_nev = 0, eig_ncv = 0, eig_which = 0, eig_keep = 0;   // MK_TRLAN, MK_LOBPCG: the tail of their long parameter block (mk_params_eig)
     uint64_t eig_seed = 0;
     int64_t n = 0;        // local rows = length of every solver vector
     int64_t nx = 0;       // length of vectors that feed an SpMV (n + halo)
@@ -232,6 +232,7 @@ mk_solver *mk_make_idr();
 mk_solver *mk_make_pcg();
 mk_solver *mk_make_mscg();
 mk_solver *mk_make_trlan();
+mk_solver *mk_make_lobpcg();
 
 #ifdef __HIPCC__
 // ------------------------------------------------------------------ small shared kernels

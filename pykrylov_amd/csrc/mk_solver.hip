@@ -293,7 +293,7 @@ void mk_solver::fill_result(mk_result *res) const {
 extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_solver **out) {
     MK_REQUIRE_INIT();
     MK_ARG(A && params && out);
-    // the short block, or a long one whose tail carries the shifts of MK_MSCG or the eigenproblem of MK_TRLAN (every kind
+    // the short block, or a long one whose tail carries the shifts of MK_MSCG or the eigenproblem of MK_TRLAN / MK_LOBPCG (every kind
     // takes any of them)
     const mk_params_shifts *shifts = nullptr;
     const mk_params_eig *eig = nullptr;
@@ -370,6 +370,35 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
             s->eig_ncv = eig->ncv;
             s->eig_which = eig->which;
             s->eig_keep = eig->keep ? eig->keep : std::min(eig->nev + (eig->ncv - eig->nev) / 2, eig->ncv - 1);
+            s->eig_seed = eig->seed;
+            break;
+        }
+        case MK_LOBPCG: {
+            if (!eig)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: LOBPCG takes nev, the block size (in ncv), which and seed in its long "
+                               "parameter block (struct_size = sizeof(mk_params_eig))");
+            if (A->ex.mode >= 0 || A->row_block)
+                return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: the operator is row-partitioned (it carries an exchange "
+                               "plan or a row block); LOBPCG is single-GPU");
+            if (params->restart != 0) {                      // the probe of the Gram kernel (a test hook: mikrylov.h)
+                if (params->restart != 1 || !(1 <= eig->ncv && eig->ncv <= 3 * MK_LOBPCG_MAX_BLOCK))
+                    return mk_fail(MK_ERR_ARG, "mk_solver_create: LOBPCG's Gram probe takes restart = 1 and 1 <= ncv <= %d columns",
+                                   3 * MK_LOBPCG_MAX_BLOCK);
+            } else {
+                const int64_t top = A->nrows / 3 < MK_LOBPCG_MAX_BLOCK ? A->nrows / 3 : MK_LOBPCG_MAX_BLOCK;
+                if (!(1 <= eig->nev && eig->nev <= eig->ncv && (int64_t)eig->ncv <= top))
+                    return mk_fail(MK_ERR_ARG, "mk_solver_create: LOBPCG nev = %d, block = %d, must be 1 <= nev <= block <= "
+                                   "min(%d, n / 3) = %lld", (int)eig->nev, (int)eig->ncv, MK_LOBPCG_MAX_BLOCK, (long long)top);
+            }
+            if (eig->keep != 0)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: LOBPCG keep = %d, must be 0", (int)eig->keep);
+            if (eig->which != 0 && eig->which != 1)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: LOBPCG which = %d, must be 0 (smallest) or 1 (largest)",
+                               (int)eig->which);
+            s = mk_make_lobpcg();
+            s->eig_nev = eig->nev;
+            s->eig_ncv = eig->ncv;
+            s->eig_which = eig->which;
             s->eig_seed = eig->seed;
             break;
         }
@@ -545,7 +574,7 @@ extern "C" int mk_solver_destroy(mk_solver *s) {
 }
 
 extern "C" int mk_solver_setup(mk_solver *s, const double *rhs, const double *guess) {
-    MK_ARG(s && (rhs || s->prm.kind == MK_TRLAN));            // (thick-restart Lanczos: no start vector selects the hashed one)
+    MK_ARG(s && (rhs || s->prm.kind == MK_TRLAN || s->prm.kind == MK_LOBPCG));   // (the eigensolvers: no start selects the hashed one)
     MK_ARG(MK_ALIGNED16(rhs) && MK_ALIGNED16(guess));        // borrowed vectors are read in 16-byte pairs
     s->q = 0;
     s->it = 0;

@@ -242,7 +242,8 @@ class DeviceRun(object):
         # `shifts`: the shifts of multi-shift CG; they travel in the long parameter block (mk_params_shifts), whose head
         # is the mk_params every kind takes.
         # `eig`: (nev, ncv, which, keep, seed) of thick-restart Lanczos, in the second long block (mk_params_eig).  For that
-        # kind `rhs` is the start vector and may be None (the hashed one).
+        # kind `rhs` is the start vector and may be None (the hashed one).  LOBPCG (MK_LOBPCG) takes the same block with the
+        # block size in `ncv`; its `rhs` is the start block, ncv * n doubles, vector after vector, or None.
         transpose = params.pop('transpose', None)
         sides = params.pop('sides', None)
         draws = params.pop('placement_draws', None)
@@ -259,16 +260,18 @@ class DeviceRun(object):
         self.n_x = n if (transpose is None or kind == _lib.MK_CRAIGMR) else op.shape[1]
         # rhs / guess: host arrays (copied to HBM) or DeviceArray objects already resident there
         self._borrowed = [b for b in (rhs, guess) if isinstance(b, _lib.DeviceArray)]
-        if rhs is None and kind == _lib.MK_TRLAN:
+        n_rhs = n * int(eig[1]) if kind == _lib.MK_LOBPCG else n
+        if rhs is None and kind in (_lib.MK_TRLAN, _lib.MK_LOBPCG):
             self.d_rhs = None
         else:
             self.d_rhs = rhs if isinstance(rhs, _lib.DeviceArray) else \
-                _lib.DeviceArray.from_numpy(as_f64_vector(rhs, n, 'rhs'))
+                _lib.DeviceArray.from_numpy(as_f64_vector(rhs, n_rhs, 'rhs'))
         self.d_guess = None if guess is None else (
             guess if isinstance(guess, _lib.DeviceArray) else
             _lib.DeviceArray.from_numpy(as_f64_vector(guess, n, 'guess')))
-        if (self.d_rhs is not None and self.d_rhs.n != n) or (self.d_guess is not None and self.d_guess.n != n):
-            raise ValueError('rhs / guess must have %d entries' % n)
+        if (self.d_rhs is not None and self.d_rhs.n != n_rhs) or (self.d_guess is not None and self.d_guess.n != n):
+            raise ValueError('rhs / guess must have %d entries' % n if n_rhs == n else
+                             'the start block must have %d entries' % n_rhs)
         if eig is not None:
             block = _lib.MkParamsEig()
             block.nev, block.ncv, block.which, block.keep, block.seed = [int(v) for v in eig]
