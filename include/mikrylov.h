@@ -375,7 +375,8 @@ typedef enum {
     MK_PCG = 13,      /* preconditioned CG, the textbook recurrence p = z + beta p (no reference module): a square solver */
     MK_MSCG = 14,     /* multi-shift CG: (A + sigma_k I) x_k = b for up to MK_MSCG_MAX_SHIFTS shifts in one Krylov space (no reference module): a square solver */
     MK_TRLAN = 15,    /* thick-restart Lanczos (Wu and Simon): the nev smallest or largest eigenpairs of a symmetric operator (no reference module); not a solver of A x = b */
-    MK_LOBPCG = 16    /* LOBPCG (Knyazev): a block, preconditioned eigensolver with soft locking for the nev smallest or largest eigenpairs of a symmetric operator (no reference module); not a solver of A x = b */
+    MK_LOBPCG = 16,   /* LOBPCG (Knyazev): a block, preconditioned eigensolver with soft locking for the nev smallest or largest eigenpairs of a symmetric operator (no reference module); not a solver of A x = b */
+    MK_TRSVD = 17     /* thick-restart Golub-Kahan-Lanczos bidiagonalisation (Baglama and Reichel): the nev largest or smallest singular triplets of a tall operator; needs mk_solver_set_transpose (no reference module); not a solver of A x = b */
 } mk_solver_kind;
 
 #define MK_GMRES_MAX_RESTART 128
@@ -403,7 +404,7 @@ typedef struct {
     double btol;              /* lsqr.py:86 */
     double conlim;            /* lsqr.py:87 */
     int32_t restart;          /* MK_GMRES: steps per cycle, 1 .. MK_GMRES_MAX_RESTART (clamped to n); MK_ERR_ARG otherwise */
-    int32_t reorth;           /* MK_GMRES: 1 = classical Gram-Schmidt twice per step, 0 = once */
+    int32_t reorth;           /* MK_GMRES: 1 = classical Gram-Schmidt twice per step, 0 = once; MK_TRSVD: 1 = both bases are orthogonalised in full, 0 = the V basis only (one-sided); MK_ERR_ARG otherwise */
 } mk_params;
 
 /* The long parameter block: mk_params followed by the shifts of MK_MSCG.  mk_params itself is unchanged, so that callers
@@ -417,15 +418,17 @@ typedef struct {
     double sigma[MK_MSCG_MAX_SHIFTS];   /* the shifts sigma_k, k < nsigma, each finite */
 } mk_params_shifts;
 
-/* The second long parameter block: mk_params followed by what the eigensolvers MK_TRLAN and MK_LOBPCG ask for.  It is told
+/* The second long parameter block: mk_params followed by what the eigensolvers MK_TRLAN and MK_LOBPCG (and MK_TRSVD) ask for.  It is told
  * apart by struct_size like the first: hand mk_solver_create `&block.base` with block.base.struct_size =
  * sizeof(mk_params_eig).  Every solver kind accepts it, only MK_TRLAN and MK_LOBPCG read the tail, and both refuse the other
  * two blocks (MK_ERR_ARG).  MK_TRLAN: MK_ERR_ARG unless 1 <= nev < ncv <= min(n, MK_TRLAN_MAX_NCV) and, for a keep that is
  * not 0, nev <= keep < ncv.  MK_LOBPCG: `ncv` carries the block size nb, MK_ERR_ARG unless
- * 1 <= nev <= nb <= min(MK_LOBPCG_MAX_BLOCK, n / 3) and keep == 0. */
+ * 1 <= nev <= nb <= min(MK_LOBPCG_MAX_BLOCK, n / 3) and keep == 0.  MK_TRSVD reads the tail as MK_TRLAN does, nev being the
+ * singular triplets wanted: MK_ERR_ARG unless 1 <= nev < ncv <= min(ncols, MK_TRLAN_MAX_NCV) and, for a keep that is not 0,
+ * nev <= keep < ncv; `which`: 0 = the smallest, 1 = the largest singular values. */
 typedef struct {
     mk_params base;
-    int32_t nev;              /* eigenpairs wanted */
+    int32_t nev;              /* eigenpairs (MK_TRSVD: singular triplets) wanted */
     int32_t ncv;              /* MK_TRLAN: basis vectors per cycle; MK_LOBPCG: the block size nb */
     int32_t which;            /* 0 = the smallest ('SA'), 1 = the largest ('LA'); MK_ERR_ARG otherwise */
     int32_t keep;             /* MK_TRLAN: Ritz vectors kept at a restart; 0 = automatic: min(nev + (ncv - nev) / 2, ncv - 1); MK_LOBPCG: must be 0 */
@@ -462,6 +465,11 @@ typedef struct {
                                * [3] bytes of the workspace allocation, [4] wanted pairs whose residual met the threshold,
                                * [5] breakdown (0 / 1), [6] Jacobi sweeps of the last small eigenproblem, [7] restarts (small
                                * problems solved again without P, and re-activations of a fully locked block) */
+                              /* MK_TRSVD: [0] cycles, [1] the ncv in use, [2] the keep in use, [3] bytes of the two basis allocations,
+                               * [4] wanted triplets whose estimate met the threshold in the last cycle, [5] breakdown: 0 none, 1 a
+                               * beta, 2 an alpha, 3 a start vector without a positive, finite norm, [6] the reorth in use,
+                               * [7] milliseconds the device spent in the last rotation of both bases; `istop` = Jacobi sweeps of
+                               * the last cycle's small SVD */
 } mk_result;
 
 typedef struct mk_solver mk_solver;
@@ -575,6 +583,42 @@ MK_API int mk_solver_set_pcg(mk_solver *s, int32_t flexible);
  * against); mk_params.restart = 1 makes the solver a probe of the Gram kernel alone: `ncv` = m, 1 .. 48, columns of n
  * doubles in the start block, set-up forms U'U (the entries on and above the diagonal, mirrored), ends the run, and
  * mk_solver_vector(0) returns the m x m result; aux[7] = the milliseconds of the Gram launches. */
+/* MK_TRSVD: thick-restart Golub-Kahan-Lanczos bidiagonalisation (Baglama and Reichel 2005) for the nev largest (which = 1) or
+ * smallest (0) singular values of a tall operator A (nrows >= ncols) with their left and right vectors.  It has no function of
+ * its own: it enters through the kind and the long parameter block mk_params_eig.  mk_solver_create: MK_ERR_ARG for the short
+ * block, the shifts block, a tail outside the ranges listed at mk_params_eig, a mk_params.reorth that is neither 0 nor 1 or a
+ * wide operator (nrows < ncols: hand it the transpose and swap the vectors); MK_ERR_UNSUPPORTED for an operator with an
+ * exchange plan or a row block (single GPU).  Every preconditioner setter, those of the least-squares solvers included,
+ * answers MK_ERR_UNSUPPORTED.  mk_solver_set_transpose hands it A' as it does for the least-squares kinds; mk_solver_setup
+ * without it is MK_ERR_STATE.
+ * mk_solver_setup(s, start_dev, NULL): the start vector, ncols doubles (the short space), borrowed for the call, or NULL for
+ * the hashed vector mk_cell_field(i, seed) - 1.0.  A guess is MK_ERR_ARG.  Both bases are allocated at the first set-up, one
+ * allocation each: U of ncv and V of ncv + 1 columns, each with 16 (ceil(keep / 16) - 1) spare ones, a column being the
+ * length (nrows for U, ncols for V) rounded up to even plus 2 doubles (MK_ERR_HIP with the sizes if one does not fit).  A
+ * start vector without a positive, finite norm, or matvec_max < 2 ncv, halts the run in set-up (MK_OK): no cycle, no
+ * triplet, breakdown 3 in the first case.
+ * One pass of mk_solver_iterate is one whole cycle, without a transfer to the host: per step u = A v_j, orthogonalised
+ * against all of U by classical Gram-Schmidt twice (reorth = 1) or against u_{j-1} alone inside the product kernel
+ * (reorth = 0, Simon and Zha's one-sided reorthogonalisation; the first step behind a restart subtracts the arrow
+ * sum_i B[i, l+1] u_i by one stream launch per 8 columns), alpha_j = ||u||, u_j = u / alpha_j, w = A' u_j orthogonalised
+ * against all of V twice (always), beta_j = ||w||, v_{j+1} = w / beta_j.  Then one download of the step scalars, the SVD of
+ * the projected upper triangular matrix B = X diag(s) Y' on the host by a one-sided Jacobi iteration (B'B is never formed),
+ * one upload of the rotation coefficients and the rotations of U by X and of V by Y on the device.
+ * est_i = |beta_last X[last, i]| is the norm of the whole residual A' u_i - s_i v_i (A v_i = s_i u_i holds to rounding);
+ * threshold = max(abstol, reltol anorm), anorm the largest singular value of a projected matrix so far.  The run ends when
+ * the nev wanted triplets all have est <= threshold (converged), at a breakdown -- an alpha_j or beta_j that is not
+ * > 2^-26 smax, smax the largest alpha or beta accepted so far: the bases span a pair of singular subspaces, every triplet
+ * is exact, converged iff they hold at least nev triplets; an alpha breakdown leaves a zero singular value, which is returned
+ * as 0 with a zero left vector -- or when the next cycle's 2 (ncv - keep) products would exceed matvec_max, which is
+ * therefore never exceeded (products with A and with A' both count).
+ * mk_solver_x = the first right vector.  mk_solver_vector(i): i < nev: right vector i (ncols doubles); nev <= i < 2 nev:
+ * left vector i - nev (nrows doubles); i = 2 nev: the record, len = 3 nev: entries 3 i, 3 i + 1, 3 i + 2 hold s_i, est_i and
+ * the cycle (from 1) at which the triplet in that place of the wanted order first met the threshold (-1: never); the
+ * triplets are in descending order of s for either `which`; one that does not exist (a breakdown with fewer than nev steps,
+ * a run halted in set-up) holds -1, 0, -1.  mk_solver_history = one entry per cycle, the largest estimate among the wanted
+ * triplets; mk_solver_history2 = per cycle the milliseconds of its host part (a measurement).  mk_result: itn = steps,
+ * nMatvec = products, converged and threshold as above, residNorm = the last history entry, residNorm0 = ||start||,
+ * Anorm = anorm, istop and aux as listed at mk_result. */
 /* Several GPUs: mark `A` as THIS rank's block of consecutive rows of a taller m x n operator (its columns are global
  * and unlocalized; no mk_csr_set_exchange).  The least-squares solvers then keep every m-space vector (rhs, u, r;
  * x of CRAIG-MR) sliced like the rows and every n-space vector (v, w, x) whole on every rank: `A * v` needs no

@@ -21,6 +21,7 @@ from .pcg import PCG                                                            
 from .mscg import ShiftedCG                                                                     # noqa: F401
 from .trlan import ThickRestartLanczos, eigsh                                                   # noqa: F401
 from .lobpcg import LOBPCG, lobpcg                                                              # noqa: F401
+from .trsvd import ThickRestartSVD, svds                                                        # noqa: F401
 from .minres import Minres                                                                      # noqa: F401
 from .symmlq import Symmlq                                                                      # noqa: F401
 from .lbfgs import InverseLBFGSOperator, LBFGSOperator, CompactLBFGSOperator                    # noqa: F401

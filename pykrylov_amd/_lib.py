@@ -29,6 +29,7 @@ MK_TRLAN = 15
 MK_TRLAN_MAX_NCV = 128
 MK_LOBPCG = 16
 MK_LOBPCG_MAX_BLOCK = 16
+MK_TRSVD = 17
 
 
 class MkParams(ctypes.Structure):
@@ -46,7 +47,8 @@ class MkParamsShifts(ctypes.Structure):
 
 class MkParamsEig(ctypes.Structure):
     """mk_params_eig (include/mikrylov.h): mk_params followed by what MK_TRLAN and MK_LOBPCG ask for (`which`: 0 = smallest,
-    1 = largest; `keep` 0 = automatic; MK_LOBPCG: `ncv` is the block size and `keep` 0); mk_solver_create takes `.base`."""
+    1 = largest; `keep` 0 = automatic; MK_LOBPCG: `ncv` is the block size and `keep` 0; MK_TRSVD: `nev` singular triplets);
+    mk_solver_create takes `.base`."""
     _fields_ = [("base", MkParams), ("nev", c_i32), ("ncv", c_i32), ("which", c_i32), ("keep", c_i32),
                 ("seed", ctypes.c_uint64)]
 

@@ -1,5 +1,5 @@
 // mk_multicol.h -- stream ops over several stored columns per launch, shared by the solvers that keep blocks of vectors
-// (GMRES' basis, mk_gmres.hip; IDR's P, G and U, mk_idr.hip; the Lanczos basis of mk_trlan.hip).  A launch takes GM_GROUP columns, so that the vector they are
+// (GMRES' basis, mk_gmres.hip; IDR's P, G and U, mk_idr.hip; the Lanczos basis of mk_trlan.hip; the two bases of mk_trsvd.hip).  A launch takes GM_GROUP columns, so that the vector they are
 // taken against is read once per group instead of once per column.
 #pragma once
 #include "mk_solver.h"
@@ -60,6 +60,51 @@ struct GmOpUpdate {
             coef[c] = mk_total(bank + (size_t)c * MK_MAXP, np, s4);
             if (lead) h[c] = add ? h[c] + coef[c] : coef[c];
         }
+        return false;
+    }
+    __device__ bool skip() const { return false; }
+    __device__ void pair(int64_t i, double *acc) {
+        double2 wv = mk_ld2(w, i);
+        double2 cv[GM_GROUP];
+#pragma unroll
+        for (int c = 0; c < GM_GROUP; ++c)
+            if (c < ncol) cv[c] = mk_ld2(v.col[c], i);
+#pragma unroll
+        for (int c = 0; c < GM_GROUP; ++c)
+            if (c < ncol) {
+                wv.x = wv.x - coef[c] * cv[c].x;
+                wv.y = wv.y - coef[c] * cv[c].y;
+            }
+        mk_st2(w, i, wv);
+        if constexpr (WW) {
+            acc[0] += wv.x * wv.x;
+            acc[0] += wv.y * wv.y;
+        }
+    }
+    __device__ void one(int64_t i, double *acc) {
+        double wv = w[i];
+#pragma unroll
+        for (int c = 0; c < GM_GROUP; ++c)
+            if (c < ncol) wv = wv - coef[c] * v.col[c][i];
+        w[i] = wv;
+        if constexpr (WW) acc[0] += wv * wv;
+    }
+};
+
+// A: U with given coefficients: w = w - y_c v_c for the columns of one group, ascending, each term a multiply and a
+// subtraction, the y_c read from a device array (the arrow of a restarted bidiagonalisation: the first step of a one-sided
+// cycle of mk_trsvd.hip).  WW: <w, w> of the result goes into the slot `partials` of the launch points at.
+template <bool WW>
+struct GmOpUpdateGiven {
+    static constexpr int NACC = WW ? 1 : 0, SLOT0 = 0;
+    const double *y;             // at the group's first coefficient
+    double *w;
+    GmCols v;
+    int ncol;
+    double coef[GM_GROUP];
+    __device__ bool prologue(double *, bool) {
+#pragma unroll
+        for (int c = 0; c < GM_GROUP; ++c) coef[c] = c < ncol ? y[c] : 0.0;
         return false;
     }
     __device__ bool skip() const { return false; }

@@ -126,7 +126,7 @@ struct MkPrecon {
 
 struct mk_solver {
     const mk_csr *A = nullptr;
-    const mk_csr *At = nullptr;     // transposed matrix (least-squares solvers only)
+    const mk_csr *At = nullptr;     // transposed matrix (the least-squares solvers and MK_TRSVD)
     MkPrecon slot[2];               // [0]: a square solver's preconditioner, or M of a least-squares one; [1]: N
     double *h_pin = nullptr, *h_pout = nullptr;   // pinned staging of the host callback, shared by the slots (max of their lengths)
     double *d_ptmp = nullptr;       // product target when a site preconditions a vector in place by a device matrix
@@ -149,7 +149,7 @@ struct mk_solver {
     mk_params prm{};
     int nsigma = 0;                              // MK_MSCG: the shifts of the long parameter block (mk_params_shifts)
     double sigma[MK_MSCG_MAX_SHIFTS] = {};
-    int eig_nev = 0, eig_ncv = 0, eig_which = 0, eig_keep = 0;   // MK_TRLAN, MK_LOBPCG: the tail of their long parameter block (mk_params_eig)
+    int eig_nev = 0, eig_ncv = 0, eig_which = 0, eig_keep = 0;   // MK_TRLAN, MK_LOBPCG, MK_TRSVD: the tail of their long parameter block (mk_params_eig)
     uint64_t eig_seed = 0;
     int64_t n = 0;        // local rows = length of every solver vector
     int64_t nx = 0;       // length of vectors that feed an SpMV (n + halo)
@@ -233,6 +233,7 @@ mk_solver *mk_make_pcg();
 mk_solver *mk_make_mscg();
 mk_solver *mk_make_trlan();
 mk_solver *mk_make_lobpcg();
+mk_solver *mk_make_trsvd();
 
 #ifdef __HIPCC__
 // ------------------------------------------------------------------ small shared kernels

@@ -9,10 +9,11 @@ int mk_solver::init_common(const mk_csr *A_, const mk_params *p) {
     A->dependents += 1;              // (borrowed for the solver's lifetime: destroying A meanwhile is deferred)
     prm = *p;
     n = A->ex.mode >= 0 ? A->ex.n_local : A->nrows;
-    const bool rectangular_ok = prm.kind >= MK_LSQR && prm.kind <= MK_CRAIGMR;
+    const bool lls = prm.kind >= MK_LSQR && prm.kind <= MK_CRAIGMR;
+    const bool rectangular_ok = lls || prm.kind == MK_TRSVD;
     slot[0].len = n;
-    slot[1].len = rectangular_ok ? A->ncols : 0;
-    if (rectangular_ok && A->ex.mode >= 0)
+    slot[1].len = lls ? A->ncols : 0;
+    if (lls && A->ex.mode >= 0)
         return mk_fail(MK_ERR_UNSUPPORTED, "the least-squares solvers partition by row blocks with a replicated column "
                        "space (mk_csr_set_row_block), not with a halo / all-gather exchange plan");
     if (!rectangular_ok && A->ex.mode < 0 && A->nrows != A->ncols)
@@ -293,7 +294,7 @@ void mk_solver::fill_result(mk_result *res) const {
 extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_solver **out) {
     MK_REQUIRE_INIT();
     MK_ARG(A && params && out);
-    // the short block, or a long one whose tail carries the shifts of MK_MSCG or the eigenproblem of MK_TRLAN / MK_LOBPCG (every kind
+    // the short block, or a long one whose tail carries the shifts of MK_MSCG or the eigenproblem of MK_TRLAN / MK_LOBPCG / MK_TRSVD (every kind
     // takes any of them)
     const mk_params_shifts *shifts = nullptr;
     const mk_params_eig *eig = nullptr;
@@ -399,6 +400,38 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
             s->eig_nev = eig->nev;
             s->eig_ncv = eig->ncv;
             s->eig_which = eig->which;
+            s->eig_seed = eig->seed;
+            break;
+        }
+        case MK_TRSVD: {
+            if (!eig)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: the thick-restart SVD takes nev (the triplets wanted), ncv, which, "
+                               "keep and seed in its long parameter block (struct_size = sizeof(mk_params_eig))");
+            if (A->ex.mode >= 0 || A->row_block)
+                return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: the operator is row-partitioned (it carries an exchange "
+                               "plan or a row block); the thick-restart SVD is single-GPU");
+            if (A->nrows < A->ncols)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: the thick-restart SVD takes a tall operator (nrows >= ncols), got "
+                               "%lld x %lld; hand it the transpose and swap the left and right vectors", (long long)A->nrows,
+                               (long long)A->ncols);
+            const int64_t top = A->ncols < MK_TRLAN_MAX_NCV ? A->ncols : MK_TRLAN_MAX_NCV;
+            if (!(1 <= eig->nev && eig->nev < eig->ncv && (int64_t)eig->ncv <= top))
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: thick-restart SVD nev = %d, ncv = %d, must be 1 <= nev < ncv <= "
+                               "min(ncols, %d) = %lld", (int)eig->nev, (int)eig->ncv, MK_TRLAN_MAX_NCV, (long long)top);
+            if (eig->keep != 0 && !(eig->nev <= eig->keep && eig->keep < eig->ncv))
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: thick-restart SVD keep = %d, must be 0 (automatic) or nev = %d "
+                               "<= keep < ncv = %d", (int)eig->keep, (int)eig->nev, (int)eig->ncv);
+            if (eig->which != 0 && eig->which != 1)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: thick-restart SVD which = %d, must be 0 (smallest) or 1 "
+                               "(largest)", (int)eig->which);
+            if (params->reorth != 0 && params->reorth != 1)
+                return mk_fail(MK_ERR_ARG, "mk_solver_create: thick-restart SVD reorth = %d, must be 1 (both bases) or 0 (the "
+                               "V basis only)", (int)params->reorth);
+            s = mk_make_trsvd();
+            s->eig_nev = eig->nev;
+            s->eig_ncv = eig->ncv;
+            s->eig_which = eig->which;
+            s->eig_keep = eig->keep ? eig->keep : std::min(eig->nev + (eig->ncv - eig->nev) / 2, eig->ncv - 1);
             s->eig_seed = eig->seed;
             break;
         }
@@ -574,7 +607,7 @@ extern "C" int mk_solver_destroy(mk_solver *s) {
 }
 
 extern "C" int mk_solver_setup(mk_solver *s, const double *rhs, const double *guess) {
-    MK_ARG(s && (rhs || s->prm.kind == MK_TRLAN || s->prm.kind == MK_LOBPCG));   // (the eigensolvers: no start selects the hashed one)
+    MK_ARG(s && (rhs || s->prm.kind == MK_TRLAN || s->prm.kind == MK_LOBPCG || s->prm.kind == MK_TRSVD));   // (the eigensolvers: no start selects the hashed one)
     MK_ARG(MK_ALIGNED16(rhs) && MK_ALIGNED16(guess));        // borrowed vectors are read in 16-byte pairs
     s->q = 0;
     s->it = 0;

@@ -243,7 +243,8 @@ class DeviceRun(object):
         # is the mk_params every kind takes.
         # `eig`: (nev, ncv, which, keep, seed) of thick-restart Lanczos, in the second long block (mk_params_eig).  For that
         # kind `rhs` is the start vector and may be None (the hashed one).  LOBPCG (MK_LOBPCG) takes the same block with the
-        # block size in `ncv`; its `rhs` is the start block, ncv * n doubles, vector after vector, or None.
+        # block size in `ncv`; its `rhs` is the start block, ncv * n doubles, vector after vector, or None.  The thick-restart
+        # SVD (MK_TRSVD) takes the block too, with `transpose`; its `rhs` is the start vector of ncols(A) entries, or None.
         transpose = params.pop('transpose', None)
         sides = params.pop('sides', None)
         draws = params.pop('placement_draws', None)
@@ -255,13 +256,15 @@ class DeviceRun(object):
         if draws is not None:
             self.placement_draws = int(draws)
         n = getattr(op, 'local_size', None) or (op.shape[0] if transpose is not None else op.shape[1])
+        if kind == _lib.MK_TRSVD:                            # (its start vector lives in the short space: ncols(A) entries)
+            n = op.shape[1]
         self.n = n                                           # entries of rhs / guess
         #  entries of the solution: ncols(A) for the least-squares kinds (CRAIG-MR's lives in m-space)
         self.n_x = n if (transpose is None or kind == _lib.MK_CRAIGMR) else op.shape[1]
         # rhs / guess: host arrays (copied to HBM) or DeviceArray objects already resident there
         self._borrowed = [b for b in (rhs, guess) if isinstance(b, _lib.DeviceArray)]
         n_rhs = n * int(eig[1]) if kind == _lib.MK_LOBPCG else n
-        if rhs is None and kind in (_lib.MK_TRLAN, _lib.MK_LOBPCG):
+        if rhs is None and kind in (_lib.MK_TRLAN, _lib.MK_LOBPCG, _lib.MK_TRSVD):
             self.d_rhs = None
         else:
             self.d_rhs = rhs if isinstance(rhs, _lib.DeviceArray) else \
