@@ -790,6 +790,54 @@ MK_API int mk_cheb_coefficients(const mk_cheb *F, double *host);
  * the preconditioner is replaced; NULL removes it.  Single GPU, MK_ERR_ARG on a size mismatch.  Call before
  * mk_solver_setup. */
 MK_API int mk_solver_set_precon_cheb(mk_solver *s, const mk_cheb *F);
+/* The third long parameter block: mk_params_eig followed by a scaled Chebyshev filter rho(A) (Zhou and Saad), the spectral
+ * transformation of MK_TRLAN.  Told apart by struct_size = sizeof(mk_params_filter); every other kind answers
+ * MK_ERR_UNSUPPORTED to it.  It adds no function: the solver creates the filter at mk_solver_create and owns it.
+ * A must be a square SYMMETRIC device matrix with CSR arrays of its own, single GPU (the caller vouches for the symmetry).
+ * [a, b] is the UNWANTED interval, a0 a reference point strictly outside it on the wanted side (a0 < a: which = 0, a0 > b:
+ * which = 1), and
+ *     rho(t) = T_d((t - c)/e) / T_d((a0 - c)/e),   e = 0.5*(b - a),  c = 0.5*(b + a),   d = degree, 1 .. MK_FILTER_MAX_DEGREE.
+ * The coefficients are computed once on the host, one rounding per operation, in this order:
+ *     sigma_1 = e/(a0 - c);  tau = 2.0/sigma_1;  p_1 = sigma_1/e;  q_1 = 0
+ *     j = 2..d:  sigma_j = 1.0/(tau - sigma_{j-1});  p_j = (2.0*sigma_j)/e;  q_j = sigma_{j-1}*sigma_j
+ * An end of the interval given as NaN is taken from the Gershgorin interval of the matrix, computed on the device:
+ * [min_r (a_rr - off_r), max_r (a_rr + off_r)], off_r = sum_{j != r} |a_rj|, each row added left to right in stored order from
+ * +0.0 (stored entries on the diagonal add up to a_rr), the minimum and the maximum taken through an order-preserving integer
+ * key.  The filter owns min(degree - 1, 2) vectors of nrows doubles.  out = rho(A) in is `degree` products of A, in the
+ * storage format A has; the row epilogue of step j = 1..d on y_{j-1} (y_0 = in) does
+ *     t = s - c*y_{j-1,r};  y_j = p_j*t;  y_j = y_j - q_j*y_{j-2,r}        (s the row sum; step 1 has no y_{-1} term)
+ * with one rounding per operation.  mk_solver_create: MK_ERR_ARG for a non-square matrix, a degree out of range, an infinite
+ * end, a >= b, an a0 that is not finite or lies inside [a, b], coefficients that are not finite, and a `which` that does not
+ * name the side a0 lies at; MK_ERR_UNSUPPORTED for operators that hold no arrays of their own, with an exchange plan or a
+ * row block.
+ * mk_solver_vector(s, nev + 1) = the filter's table, 5 + 2 degree + 8 doubles: a, b and a0 as used, c, e, p_1, q_1, ..., p_d,
+ * q_d, then rows, degree, the wanted side (0 smallest, 1 largest), launches per apply, device bytes held, set-up time (us),
+ * whether a / b is the Gershgorin end.
+ * The filtered cycle, per cycle:
+ *   - the product of every Lanczos step is the filter (d launches); orthogonalisation, the small eigenproblem and the
+ *     rotation are unchanged; B's Ritz values are taken in descending order whatever `which` says (rho is positive and
+ *     monotone on the wanted side);
+ *   - B's estimates |beta S[last, i]| <= max(abstol, reltol anorm_B) only open a gate.  Once the gate has been met, and in
+ *     the last cycle the budget allows, the restart rotation is followed by the verification on A: for each of the first nev
+ *     kept vectors x one product of A, theta = <x, A x>, and ||A x - theta x||; the run has converged when every such norm is
+ *     at most max(abstol, reltol anorm_A), anorm_A = max(|a|, |b|, |a0|).  Otherwise it goes on from the restart;
+ *   - nMatvec counts every product of A (filter steps and verification); a cycle starts only if its (ncv - l) d + nev products
+ *     fit into matvec_max (l = 0 in the first cycle, keep afterwards; mk_solver_setup answers MK_ERR_ARG if the first does not).
+ * The record (mk_solver_vector(nev)) holds theta_A ascending, the true A-residual norms (NaN where none was computed) and the
+ * cycle at which B's estimate first met the gate; mk_solver_vector(i) the verified vectors in that order; mk_solver_history one
+ * entry per cycle, the largest A-residual where the cycle was verified and B's largest estimate otherwise.  mk_result:
+ * residNorm the last history entry, threshold and Anorm those of A, aux[4] the pairs whose A-residual met the threshold.
+ * The probe (mk_params.restart = 1 with this block): no Lanczos run; mk_solver_setup(s, in_dev, NULL) enqueues
+ * out = rho(A) in, `in` unchanged, and ends the run; mk_solver_x = out (owned by the solver, overwritten by the next
+ * set-up); `which` is not compared with the side.  It is how tools.ChebyshevFilter applies the filter to a vector. */
+#define MK_FILTER_MAX_DEGREE 128
+typedef struct {
+    mk_params_eig eig;
+    int32_t degree;           /* 1 .. MK_FILTER_MAX_DEGREE */
+    int32_t filter_reserved;
+    double a, b;              /* the unwanted interval; NaN: the Gershgorin end */
+    double a0;                /* the reference point */
+} mk_params_filter;
 /* FSAI (factorized sparse approximate inverse, Kolotilina and Yeremin) of a square, symmetric positive definite device
  * matrix A ~ L L': a sparse lower-triangular G ~ L^-1 on a fixed pattern, computed on the device; the preconditioner is
  * M^-1 = G' G.  A owns CSR arrays with sorted rows and no duplicates (as for mk_ilu0_create); it is read during the call only

@@ -53,6 +53,12 @@ class MkParamsEig(ctypes.Structure):
                 ("seed", ctypes.c_uint64)]
 
 
+class MkParamsFilter(ctypes.Structure):
+    """mk_params_filter (include/mikrylov.h): mk_params_eig followed by the Chebyshev filter of MK_TRLAN -- its degree, the
+    unwanted interval [a, b] (NaN: the Gershgorin end) and the reference point a0; mk_solver_create takes `.eig.base`."""
+    _fields_ = [("eig", MkParamsEig), ("degree", c_i32), ("filter_reserved", c_i32), ("a", c_f64), ("b", c_f64), ("a0", c_f64)]
+
+
 class MkRowOp(ctypes.Structure):
     "mk_rowop (include/mikrylov.h): one step of a composed operator."
     _fields_ = [("code", ctypes.c_int32), ("has_scale", ctypes.c_int32), ("scale", ctypes.c_double),
@@ -63,6 +69,8 @@ MK_ILU_INFO_LEN = 12      # entries of mk_ilu_info (include/mikrylov.h)
 MK_LBFGS_INFO_LEN = 12    # entries of mk_lbfgs_info
 MK_CHEB_INFO_LEN = 8      # entries of mk_cheb_info
 MK_CHEB_MAX_DEGREE = 64   # highest degree of mk_cheb_create
+MK_FILTER_INFO_LEN = 8    # info entries behind the coefficients in a filter's table (mk_params_filter)
+MK_FILTER_MAX_DEGREE = 128   # highest degree of mk_params_filter
 MK_LANCZOS_INFO_LEN = 5   # entries of mk_csr_lanczos' info
 MK_FSAI_INFO_LEN = 8      # entries of mk_fsai_info
 MK_FSAI_MAX_ROW = 32      # longest pattern row of mk_fsai_create

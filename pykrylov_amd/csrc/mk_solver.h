@@ -65,6 +65,15 @@ struct MkDeviceOp {
 
 // A Chebyshev object as the device operator it is (mk_cheb.hip): the smoother of every level of mk_amg.hip
 const MkDeviceOp *mk_cheb_as_op(const mk_cheb *F);
+// A Chebyshev filter as the device operator it is (mk_chebfilt.hip), and what the filtered cycle of mk_trlan.hip asks of it:
+// its matrix, its degree, the unwanted interval [a, b] and the reference point a0
+struct mk_filter;
+constexpr int MK_FILTER_INFO_LEN = 8;
+int mk_filter_create(const mk_csr *A, int32_t degree, double a, double b, double a0, mk_filter **out);
+void mk_filter_free(mk_filter *F);
+const MkDeviceOp *mk_filter_as_op(const mk_filter *F);
+void mk_filter_describe(const mk_filter *F, const mk_csr **A, int *degree, double *a, double *b, double *a0);
+std::vector<double> mk_filter_table(const mk_filter *F);
 
 // A preconditioner slot.  A solver has two (mk_solver::slot): a square solver uses the first, a least-squares solver both,
 // for M (nrows(A) entries) and N (ncols(A) entries).  A diagonal is multiplied inside the loop's kernels (`d`).  With one of
@@ -191,6 +200,11 @@ struct mk_solver {
     virtual const double *vector(int) const { return nullptr; }
     virtual int64_t vector_len(int) const { return n; }   // entries of `vector(i)` (multi-shift CG's record is not a solver vector)
     virtual bool takes_precon() const { return false; }
+    // the tail of mk_params_filter: a Chebyshev filter as the spectral transformation of the loop (MK_TRLAN only)
+    virtual int make_filter(int32_t, double, double, double) {
+        return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: this solver kind takes no spectral transformation (the block "
+                       "mk_params_filter is thick-restart Lanczos', MK_TRLAN)");
+    }
     virtual bool is_fused() const { return false; }   // CG on a format-9 matrix: the x / p update rides in the next product kernel
     // work a loop defers beyond its passes (CG: the x update over a ring of directions): `drain` enqueues what is applicable at
     // the end of an iterate call, inside its timed region; `unapplied` counts completed passes whose update is still missing

@@ -298,7 +298,11 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
     // takes any of them)
     const mk_params_shifts *shifts = nullptr;
     const mk_params_eig *eig = nullptr;
-    if (params->struct_size == (int32_t)sizeof(mk_params_shifts)) shifts = reinterpret_cast<const mk_params_shifts *>(params);
+    const mk_params_filter *filt = nullptr;                  // ... or, behind the eigenproblem, the Chebyshev filter of MK_TRLAN
+    if (params->struct_size == (int32_t)sizeof(mk_params_filter)) {
+        filt = reinterpret_cast<const mk_params_filter *>(params);
+        eig = &filt->eig;
+    } else if (params->struct_size == (int32_t)sizeof(mk_params_shifts)) shifts = reinterpret_cast<const mk_params_shifts *>(params);
     else if (params->struct_size == (int32_t)sizeof(mk_params_eig)) eig = reinterpret_cast<const mk_params_eig *>(params);
     else MK_ARG(params->struct_size == (int32_t)sizeof(mk_params));
     mk_solver *s = nullptr;
@@ -440,7 +444,10 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
     if (!s) return mk_fail(MK_ERR_UNSUPPORTED, "mk_solver_create: solver kind %d is not available", params->kind);
     // (before the partial-sum counts are sized for the format in use; PCG's and multi-shift CG's product kernels are CG's,
     //  mk_cg_epi.h)
-    mk_csr_march_pref(A, params->kind == MK_CG || params->kind == MK_PCG || params->kind == MK_MSCG ? 1 : 0);
+    // (the probe of a Chebyshev filter is no loop on A: it neither states a preference nor counts as a user, so a CG solver's
+    //  format-11 matrix keeps its format and the filter's steps take the gather kernel on it, mk_chebfilt.hip)
+    const bool probe = filt && params->kind == MK_TRLAN && params->restart == 1;
+    if (!probe) mk_csr_march_pref(A, params->kind == MK_CG || params->kind == MK_PCG || params->kind == MK_MSCG ? 1 : 0);
     if (shifts && params->kind == MK_MSCG) {
         s->nsigma = shifts->nsigma;
         memcpy(s->sigma, shifts->sigma, sizeof(double) * (size_t)shifts->nsigma);
@@ -450,8 +457,14 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
         delete s;
         return rc;
     }
-    mk_csr_count_users(A, 1);
-    s->counted_user = true;
+    if (!probe) {
+        mk_csr_count_users(A, 1);
+        s->counted_user = true;
+    }
+    if (filt && (rc = s->make_filter(filt->degree, filt->a, filt->b, filt->a0)) != MK_OK) {
+        delete s;
+        return rc;
+    }
     *out = s;
     return MK_OK;
 }

@@ -21,6 +21,11 @@
 // one output column at a time into spare columns -- V is read once per output column; same bits; what tools/trlan_bench.py
 // measures R against.)
 //
+// With a Chebyshev filter (the block mk_params_filter, mk_chebfilt.hip; the restatement is tests/_chebfilt_ref.py) P is
+// w = rho(A) v_j, `degree` launches of the product kernel, and the cycle wants B's largest Ritz values whatever `which` says.
+// B's estimates only open a gate: once it has been met, and in the last cycle the budget allows, the restart rotation is
+// followed by the verification on A (`verify`): per wanted vector one plain product, <x, A x>, and ||A x - theta x||.
+//
 // Launches per step: 1 + 4 ceil(j / GM_GROUP) + 2.  Bytes per step: the product + 2 (16 j + 24 ceil(j / GM_GROUP)) n + 16 n.
 // Bytes per rotation of kk columns: 8 n (m ceil(kk / TR_KT) + kk), plus 16 n per column copied down (kk > TR_KT).
 // Every operation rounds on its own (-ffp-contract=off); every dot has the lanes, the grid and the tree of
@@ -102,9 +107,9 @@ __global__ __launch_bounds__(MK_BLOCK) void tr_start_kernel(const double *rr_par
     }
 }
 
-// E: the end of the step on column jc (0-based), whose product was the run's product number nmv
+// E: the end of the step on column jc (0-based), after which the run has made nmv products; `later`: not the run's first step
 __global__ __launch_bounds__(MK_BLOCK) void tr_step_kernel(const double *ww_part, int np, double *scal, TrScal ts, MkStatus *st,
-                                                           MkHalt halt, int jc, int64_t nmv) {
+                                                           MkHalt halt, int jc, int64_t nmv, int later) {
     __shared__ double s4[4];
     if (halt.in()) {
         if (threadIdx.x == 0) halt.out(true);
@@ -114,7 +119,7 @@ __global__ __launch_bounds__(MK_BLOCK) void tr_step_kernel(const double *ww_part
     if (threadIdx.x == 0) {
         const double alpha = ts.h[jc];
         double tm = fabs(alpha);
-        if (nmv > 1) tm = tm + scal[S_BETA];                   // (beta_j: of the step before, in this cycle or the last one)
+        if (later) tm = tm + scal[S_BETA];                    // (beta_j: of the step before, in this cycle or the last one)
         const double t0 = scal[S_TMAX];
         const double tmax = tm > t0 ? tm : t0;
         const bool stop = !(beta > 0x1.0p-26 * tmax);
@@ -128,6 +133,40 @@ __global__ __launch_bounds__(MK_BLOCK) void tr_step_kernel(const double *ww_part
         st->nMatvec = nmv;
         halt.out(stop);
     }
+}
+
+// Verification of a filtered run (mk_params_filter) on A itself: w = A x by the plain product, <x, w> by MkOpDot, then
+//   t = w - theta x, theta the total of that dot; partial <t, t>; the lead lane leaves theta in the record
+struct TrOpResid {
+    static constexpr int NACC = 1, SLOT0 = 1;
+    const double *part;         // slot 0: the partials of <x, A x>
+    int np;
+    const double *x, *w;
+    double *rec;                // rec[0] = theta
+    double theta;
+    __device__ bool prologue(double *s4, bool lead) {
+        theta = mk_total(part, np, s4);
+        if (lead) rec[0] = theta;
+        return false;
+    }
+    __device__ bool skip() const { return false; }
+    __device__ void pair(int64_t i, double *acc) {
+        const double2 xv = mk_ld2(x, i), wv = mk_ld2(w, i);
+        const double t0 = wv.x - theta * xv.x, t1 = wv.y - theta * xv.y;
+        acc[0] += t0 * t0;
+        acc[0] += t1 * t1;
+    }
+    __device__ void one(int64_t i, double *acc) {
+        const double t = w[i] - theta * x[i];
+        acc[0] += t * t;
+    }
+};
+
+// rec[1] = ||A x - theta x|| from the partials TrOpResid left in slot 1
+__global__ __launch_bounds__(MK_BLOCK) void tr_resid_kernel(const double *rr_part, int np, double *rec) {
+    __shared__ double s4[4];
+    const double r = __dsqrt_rn(mk_total(rr_part, np, s4));
+    if (threadIdx.x == 0) rec[1] = r;
 }
 
 // (R, tr_rotate_kernel, and the Jacobi solver of the small eigenproblem, tr_jacobi, live in mk_rotate.h: LOBPCG shares them)
@@ -152,9 +191,25 @@ struct TrlanSolver : mk_solver {
     bool finished = false, rotated = false;
     int64_t nmv = 0;
     double anorm = 0.0, threshold = 0.0, resid = 0.0, b0 = 0.0, rot_ms = 0.0;
+    int64_t steps = 0;               // Lanczos steps enqueued so far
+    // the filtered cycle (mk_params_filter): Lanczos on B = rho(A), verified on A
+    mk_filter *filt = nullptr;       // (owned)
+    const MkDeviceOp *fop = nullptr; // the filter as the device operator it is
+    int fdeg = 0;
+    bool probe = false;              // mk_params.restart = 1: set-up applies the filter to its vector and ends the run
+    double *d_ftab = nullptr;        // the filter's table (mk_solver_vector(nev + 1))
+    int64_t ntab = 0;
+    double anorm_a = 0.0, thr_a = 0.0;   // max(|a|, |b|, |a0|) and max(abstol, reltol anorm_a): fixed for the run
+    double *d_vpart = nullptr;       // two slots of partial sums, then 2 nev doubles: theta_i and ||A x_i - theta_i x_i||
+    bool verifying = false;          // B's gate has been met: every cycle from now on is verified on A
+    std::vector<double> th_a, res_a; // ... of the last verification, by kept column
+    std::vector<int> perm;           // returned pair i (theta_A ascending) is kept column perm[i]
 
     ~TrlanSolver() override {
         if (mk_ctx().ready) hipStreamSynchronize(mk_ctx().stream);
+        hipFree(d_vpart);
+        hipFree(d_ftab);
+        if (filt) mk_filter_free(filt);
         hipFree(d_V);
         hipFree(d_tscal);
         hipFree(d_tpart);
@@ -170,6 +225,35 @@ struct TrlanSolver : mk_solver {
     double *ww_part() const { return d_tpart + (size_t)2 * nslot * MK_MAXP; }
     double *rr_part() const { return ww_part() + MK_MAXP; }
     double *d_rec() const { return d_tscal + (size_t)3 * m; }
+    double *d_vrec() const { return d_vpart + (size_t)2 * MK_MAXP; }
+
+    // The tail of mk_params_filter (mk_solver_create): the solver creates the filter and owns it.  prm.restart = 1 is the
+    // probe -- no Lanczos run, set-up applies the filter to its vector --, whose `which` means nothing.
+    int make_filter(int32_t degree, double a, double b, double a0) override {
+        if (prm.restart != 0 && prm.restart != 1)
+            return mk_fail(MK_ERR_ARG, "mk_solver_create: thick-restart Lanczos with a filter takes restart = 0 (the solver) or 1 "
+                           "(the probe), got %d", (int)prm.restart);
+        mk_filter *F = nullptr;
+        int rc = mk_filter_create(A, degree, a, b, a0, &F);
+        if (rc != MK_OK) return rc;
+        const mk_csr *FA = nullptr;
+        mk_filter_describe(F, &FA, &fdeg, &a, &b, &a0);
+        probe = prm.restart == 1;
+        if (!probe && (a0 > b ? 1 : 0) != eig_which) {
+            mk_filter_free(F);
+            return mk_fail(MK_ERR_ARG, "mk_solver_create: the filter's reference point lies %s its interval: it wants the %s "
+                           "eigenvalues, `which` the %s", a0 > b ? "above" : "below", a0 > b ? "largest" : "smallest",
+                           eig_which ? "largest" : "smallest");
+        }
+        filt = F;
+        fop = mk_filter_as_op(F);
+        anorm_a = std::max(std::fabs(a), std::max(std::fabs(b), std::fabs(a0)));
+        const std::vector<double> t = mk_filter_table(F);
+        ntab = (int64_t)t.size();
+        MK_HIP(hipMalloc((void **)&d_ftab, sizeof(double) * t.size()));
+        MK_HIP(hipMemcpy(d_ftab, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
+        return MK_OK;
+    }
 
     template <class Op>
     void launch(const Op &op, double *partials) {
@@ -223,11 +307,39 @@ struct TrlanSolver : mk_solver {
     int setup(const double *start, const double *guess) override {
         if (guess)
             return mk_fail(MK_ERR_ARG, "mk_solver_setup: thick-restart Lanczos takes a start vector and no initial guess");
+        if (probe) {
+            if (!start) return mk_fail(MK_ERR_ARG, "mk_solver_setup: the filter probe takes the vector to apply the filter to");
+            int prc;
+            if (!d_w && (prc = alloc_vec(&d_w, n)) != MK_OK) return prc;
+            if ((prc = fop->enqueue(start, d_w, stream, nullptr, nullptr)) != MK_OK) return prc;
+            static const int up[2] = {1, 1};
+            MK_HIP(hipMemcpyAsync(d_halt, up, sizeof(up), hipMemcpyHostToDevice, stream));
+            MK_HIP(hipStreamSynchronize(stream));
+            finished = true;
+            return MK_OK;
+        }
         if (prm.matvec_max < (int64_t)eig_ncv)
             return mk_fail(MK_ERR_ARG, "mk_solver_setup: thick-restart Lanczos matvec_max = %lld is below ncv = %d: the first cycle "
                            "does not fit", (long long)prm.matvec_max, eig_ncv);
+        if (filt && prm.matvec_max < (int64_t)eig_ncv * fdeg + eig_nev)
+            return mk_fail(MK_ERR_ARG, "mk_solver_setup: filtered thick-restart Lanczos matvec_max = %lld is below ncv * degree + "
+                           "nev = %lld: the first cycle and its verification do not fit", (long long)prm.matvec_max,
+                           (long long)eig_ncv * fdeg + eig_nev);
         int rc;
         if (!allocated && (rc = allocate()) != MK_OK) return rc;
+        if (filt && !d_vpart) {
+            const size_t vb = sizeof(double) * ((size_t)2 * MK_MAXP + (size_t)2 * eig_nev);
+            MK_HIP(hipMalloc((void **)&d_vpart, vb));
+            MK_HIP(hipMemsetAsync(d_vpart, 0, vb, stream));
+        }
+        verifying = false;
+        steps = 0;
+        th_a.assign(nev, 0.0);
+        res_a.assign(nev, 0.0);
+        perm.resize(nev);
+        for (int i = 0; i < nev; ++i) perm[i] = i;
+        const double rel_a = prm.reltol * anorm_a;
+        thr_a = rel_a > prm.abstol ? rel_a : prm.abstol;
         MK_HIP(hipMemsetAsync(d_tscal, 0, sizeof(double) * ((size_t)3 * m + (size_t)3 * nev), stream));
         T.assign((size_t)m * m, 0.0);
         ja.assign((size_t)m * m, 0.0);
@@ -253,8 +365,14 @@ struct TrlanSolver : mk_solver {
     }
 
     void enqueue_step(int jc) {
-        mk_launch_spmv(this, col(jc), MkPlainEpi{d_w});
-        nmv += 1;
+        if (filt) {                                            // w = rho(A) v_j: fdeg products under the loop's halt words
+            const int rc = fop->enqueue(col(jc), d_w, stream, d_halt, &q);
+            if (rc != MK_OK && mk_ctx().pending_rc == MK_OK) mk_ctx().pending_rc = rc;
+            nmv += fdeg;
+        } else {
+            mk_launch_spmv(this, col(jc), MkPlainEpi{d_w});
+            nmv += 1;
+        }
         const int ncol = jc + 1;
         for (int p = 0; p < 2; ++p) {
             for (int c0 = 0; c0 < ncol; c0 += GM_GROUP) {
@@ -273,7 +391,8 @@ struct TrlanSolver : mk_solver {
             }
         }
         hipLaunchKernelGGL(tr_step_kernel, dim3(1), dim3(MK_BLOCK), 0, stream, ww_part(), np_stream, d_scal, ts, d_status,
-                           next_halt(), jc, nmv);
+                           next_halt(), jc, nmv, steps > 0 ? 1 : 0);
+        steps += 1;
         launch(TrOpScale{d_scal + S_BETA, d_w, col(jc + 1), 0.0}, rr_part());   // v_{j+1} = (1 / beta_{j+1}) w
     }
 
@@ -376,7 +495,9 @@ struct TrlanSolver : mk_solver {
         const double rel = prm.reltol * anorm;
         threshold = rel > prm.abstol ? rel : prm.abstol;
         const int nret = nev < me ? nev : me;
-        const auto wanted = [&](int i) { return which == 0 ? i : me - 1 - i; };   // sorted position of the i-th wanted pair
+        // (a filtered run wants B's largest whatever `which` says: rho is positive and monotone on the wanted side)
+        const int ord = filt ? 1 : which;
+        const auto wanted = [&](int i) { return ord == 0 ? i : me - 1 - i; };   // sorted position of the i-th wanted pair
         resid = 0.0;
         nconv = 0;
         for (int i = 0; i < nret; ++i) {
@@ -392,6 +513,64 @@ struct TrlanSolver : mk_solver {
         const auto host_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
         conv = (nret == nev && nconv == nev) ? 1 : 0;
         std::vector<int> pick;
+        // the restart: the first `keep` of the wanted order stay
+        const auto restart = [&]() -> int {
+            for (int i = 0; i < keep; ++i) pick.push_back(colof[wanted(i)]);
+            const int rrc = rotate(m, pick.data(), keep);
+            if (rrc != MK_OK) return rrc;
+            MK_HIP(hipMemcpyAsync(col(keep), col(m), sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+            std::fill(T.begin(), T.end(), 0.0);
+            for (int i = 0; i < keep; ++i) {
+                T[(size_t)i * m + i] = theta[wanted(i)];
+                T[(size_t)i * m + keep] = T[(size_t)keep * m + i] = blast * js[(size_t)(m - 1) * m + pick[i]];
+            }
+            l = keep;
+            return MK_OK;
+        };
+        if (filt) {
+            // B's estimates are a gate only.  The rotation first -- the restart's, whose first nev columns are the wanted Ritz
+            // vectors in B's descending order (after a breakdown: those vectors alone) --, then, once the gate has been met and
+            // in the last cycle the budget allows, the verification on A; the run goes on from the restart if that fails.
+            const bool gate = conv != 0;
+            conv = 0;
+            if (gate) verifying = true;
+            if (breakdown) nmv = h_status->nMatvec;            // (the launches behind the breakdown did nothing)
+            const int64_t cost = (int64_t)(m - keep) * fdeg + nev;   // the next cycle and the verification it may need
+            int nx = nev;
+            if (breakdown) {
+                nx = nret;
+                for (int i = 0; i < nret; ++i) pick.push_back(colof[wanted(i)]);
+                if ((rc = rotate(me, pick.data(), nret)) != MK_OK) return rc;
+            } else if ((rc = restart()) != MK_OK) {
+                return rc;
+            }
+            if (breakdown || verifying || nmv + cost > prm.matvec_max) {
+                if ((rc = verify(nx)) != MK_OK) return rc;
+                resid = 0.0;
+                nconv = 0;
+                for (int i = 0; i < nx; ++i) {
+                    if (!(res_a[i] <= resid)) resid = res_a[i];
+                    if (res_a[i] <= thr_a) nconv += 1;
+                }
+                hist.back() = resid;
+                conv = (nx == nev && nconv == nev) ? 1 : 0;
+                if (conv || breakdown || nmv + cost > prm.matvec_max) {
+                    for (int i = 0; i < nev; ++i) {
+                        const bool have = i < nx;
+                        h_Y[3 * i] = have ? th_a[perm[i]] : std::nan("");
+                        h_Y[3 * i + 1] = have ? res_a[perm[i]] : std::nan("");
+                        h_Y[3 * i + 2] = have ? (double)first_met[perm[i]] : -1.0;
+                    }
+                    MK_HIP(hipMemcpyAsync(d_rec(), h_Y, sizeof(double) * (size_t)3 * nev, hipMemcpyHostToDevice, stream));
+                    static const int up[2] = {1, 1};
+                    MK_HIP(hipMemcpyAsync(d_halt, up, sizeof(up), hipMemcpyHostToDevice, stream));
+                    MK_HIP(hipStreamSynchronize(stream));
+                    finished = true;
+                }
+            }
+            hist2.back() = host_ms();
+            return MK_OK;
+        }
         if (conv || breakdown || nmv + (int64_t)(m - keep) > prm.matvec_max) {
             // the end: X = V S[:, wanted] in ascending order of theta, the record, and the halt words for the driver
             for (int i = 0; i < nret; ++i) pick.push_back(colof[which == 0 ? i : me - nret + i]);
@@ -413,17 +592,39 @@ struct TrlanSolver : mk_solver {
             finished = true;
             return MK_OK;
         }
-        // the restart: the first `keep` of the wanted order stay
-        for (int i = 0; i < keep; ++i) pick.push_back(colof[wanted(i)]);
-        if ((rc = rotate(m, pick.data(), keep)) != MK_OK) return rc;
-        MK_HIP(hipMemcpyAsync(col(keep), col(m), sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-        std::fill(T.begin(), T.end(), 0.0);
-        for (int i = 0; i < keep; ++i) {
-            T[(size_t)i * m + i] = theta[wanted(i)];
-            T[(size_t)i * m + keep] = T[(size_t)keep * m + i] = blast * js[(size_t)(m - 1) * m + pick[i]];
-        }
-        l = keep;
+        if ((rc = restart()) != MK_OK) return rc;
         hist2.back() = host_ms();
+        return MK_OK;
+    }
+
+    // The verification of a filtered run: theta_i = <x_i, A x_i> and ||A x_i - theta_i x_i|| for the kept columns i < nx, by
+    // launches that no halt word stops (a breakdown has raised them), then the 2 nx scalars come down; `perm` orders the
+    // columns by theta ascending (ties by column).  The residual is formed from A x - theta x itself: <A x, A x> - theta^2
+    // cancels at 1e-8 ||A||.
+    int verify(int nx) {
+        const auto nohalt = [&] { return MkHalt{d_nohalt, 0, 0}; };
+        for (int i = 0; i < nx; ++i) {
+            mk_spmv_launch_blocks(A, mk_grid_spmv_for(A), stream, col(i), MkPlainEpi{d_w}, MkNoGate(), nohalt, d_part);
+            hipLaunchKernelGGL(mk_stream_kernel<MkOpDot<0>>, dim3(mk_grid_stream(n)), dim3(MK_BLOCK), 0, stream,
+                               MkOpDot<0>{col(i), d_w}, n, nohalt(), d_vpart);
+            hipLaunchKernelGGL(mk_stream_kernel<TrOpResid>, dim3(mk_grid_stream(n)), dim3(MK_BLOCK), 0, stream,
+                               TrOpResid{d_vpart, np_stream, col(i), d_w, d_vrec() + 2 * i, 0.0}, n, nohalt(), d_vpart);
+            hipLaunchKernelGGL(tr_resid_kernel, dim3(1), dim3(MK_BLOCK), 0, stream, d_vpart + MK_MAXP, np_stream, d_vrec() + 2 * i);
+        }
+        nmv += nx;
+        MK_HIP(hipGetLastError());
+        MK_HIP(hipMemcpyAsync(h_ab, d_vrec(), sizeof(double) * (size_t)2 * nx, hipMemcpyDeviceToHost, stream));
+        MK_HIP(hipStreamSynchronize(stream));
+        if (mk_ctx().pending_rc != MK_OK) return mk_ctx().pending_rc;
+        for (int i = 0; i < nx; ++i) {
+            th_a[i] = h_ab[2 * i];
+            res_a[i] = h_ab[2 * i + 1];
+            if (!std::isfinite(th_a[i]) || !std::isfinite(res_a[i]))
+                return mk_fail(MK_ERR_ARG, "thick-restart Lanczos: the verification of pair %d on A is not finite (theta = %g, "
+                               "residual = %g)", i + 1, th_a[i], res_a[i]);
+        }
+        for (int i = 0; i < nev; ++i) perm[i] = i;
+        std::stable_sort(perm.begin(), perm.begin() + nx, [&](int x, int y) { return th_a[x] < th_a[y]; });
         return MK_OK;
     }
 
@@ -451,15 +652,22 @@ struct TrlanSolver : mk_solver {
         res->aux[5] = (double)breakdown;
         res->aux[6] = (double)sweeps;
         res->aux[7] = rot_ms;
+        if (filt) {                                            // (the host's count: the verification's products are in it)
+            res->nMatvec = nmv;
+            res->threshold = thr_a;
+            res->Anorm = anorm_a;
+        }
         return MK_OK;
     }
 
-    const double *x() const override { return d_V; }
+    // (a filtered run leaves its vectors where the restart rotation put them, in B's descending order: `perm` finds them)
+    const double *x() const override { return probe ? d_w : (filt && allocated ? col(perm[0]) : d_V); }
     const double *vector(int i) const override {
+        if (filt && i == eig_nev + 1) return d_ftab;
         if (!allocated || i < 0 || i > nev) return nullptr;
-        return i < nev ? col(i) : d_rec();
+        return i < nev ? col(filt ? perm[i] : i) : d_rec();
     }
-    int64_t vector_len(int i) const override { return i == nev ? 3 * (int64_t)nev : n; }
+    int64_t vector_len(int i) const override { return filt && i == eig_nev + 1 ? ntab : (i == nev ? 3 * (int64_t)nev : n); }
 };
 
 }  // namespace

@@ -252,6 +252,10 @@ class DeviceRun(object):
         self.pcg = params.pop('pcg', None)
         shifts = params.pop('shifts', None)
         eig = params.pop('eig', None)
+        # `filter`: (degree, a, b, a0) of the Chebyshev filter of thick-restart Lanczos, the tail of the third long block
+        # (mk_params_filter) behind `eig`; an end of [a, b] that is None or NaN is the Gershgorin end.  With `restart=1` the
+        # run is the filter's probe: set-up applies the filter to `rhs`, `x()` is the result.
+        self.filter = params.pop('filter', None)
         self._d_shadow = None
         if draws is not None:
             self.placement_draws = int(draws)
@@ -275,7 +279,14 @@ class DeviceRun(object):
         if (self.d_rhs is not None and self.d_rhs.n != n_rhs) or (self.d_guess is not None and self.d_guess.n != n):
             raise ValueError('rhs / guess must have %d entries' % n if n_rhs == n else
                              'the start block must have %d entries' % n_rhs)
-        if eig is not None:
+        if eig is not None and self.filter is not None:
+            block = self._block = _lib.MkParamsFilter()
+            block.eig.nev, block.eig.ncv, block.eig.which, block.eig.keep, block.eig.seed = [int(v) for v in eig]
+            block.degree = int(self.filter[0])
+            block.a, block.b, block.a0 = [float('nan') if v is None else float(v) for v in self.filter[1:]]
+            p = block.eig.base                               # (a view: it writes into the block and keeps it alive)
+            p.struct_size = ctypes.sizeof(_lib.MkParamsFilter)
+        elif eig is not None:
             block = _lib.MkParamsEig()
             block.nev, block.ncv, block.which, block.keep, block.seed = [int(v) for v in eig]
             p = block.base                                   # (a view: it writes into the block and keeps it alive)

@@ -1,5 +1,6 @@
 """Small helpers of the solver path (reference pykrylov/tools/utils.py)."""
 import ctypes
+import math
 
 import numpy as np
 
@@ -469,6 +470,195 @@ class ChebyshevPreconditioner(DevicePreconditioner):
         "``(c0, c1, c2)``: the scalar of the first direction and the two coefficient arrays of the steps 1 .. degree."
         c = self._coefficients(self._live(), self.degree)
         return float(c[2]), c[3::2].copy(), c[4::2].copy()
+
+
+def _filter_end(what, name, v):
+    "An end of a filter's interval: None (the Gershgorin end, NaN for the library) or a finite number."
+    if v is None:
+        return float('nan')
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+        raise ValueError('%s: %s must be None (the Gershgorin end) or a finite number, got %r' % (what, name, v))
+    return float(v)
+
+
+def cheb_filter(op, degree=16, interval=(None, None), ref=None):
+    """The scaled Chebyshev filter ``y = rho(A) x`` of Zhou and Saad for a symmetric device matrix (a :class:`CsrOperator`
+    declared ``symmetric=True``), resident on the device: the spectral transformation of :class:`ThickRestartLanczos`
+    (``solve(..., filter=F)``).  ``interval = (a, b)`` is the UNWANTED part of the spectrum and `ref` = a0 a reference point
+    strictly outside it on the wanted side (``a0 < a``: the smallest eigenvalues are wanted, ``a0 > b``: the largest);
+    ``rho(t) = T_d((t - c)/e) / T_d((a0 - c)/e)`` with ``e = (b - a)/2``, ``c = (b + a)/2``, ``d = degree`` (1 .. 128) is
+    below ``1 / T_d((a0 - c)/e)`` in modulus on ``[a, b]`` and grows monotonically beyond the end `ref` lies at.  An end
+    given as None is the Gershgorin end of the matrix, computed on the device.  An apply is `degree` products of `op` in the
+    storage format it has, the vector work fused into the product's row epilogue.
+
+    An eigenvalue of `A` inside ``[a, b]`` is damped, not found: `interval` must leave the wanted eigenvalues outside
+    (:func:`cheb_filter_for` chooses an interval that does)."""
+    _device_matrix(op, 'cheb_filter', 'the Chebyshev filter')
+    degree = _checked_int('cheb_filter', 'degree', degree, 1, _lib.MK_FILTER_MAX_DEGREE)
+    try:
+        a, b = interval
+    except (TypeError, ValueError):
+        raise ValueError('cheb_filter: interval must be a pair (a, b), got %r' % (interval,))
+    a, b = _filter_end('cheb_filter', 'interval[0]', a), _filter_end('cheb_filter', 'interval[1]', b)
+    if ref is None or np.isnan(_filter_end('cheb_filter', 'ref', ref)):
+        raise ValueError('cheb_filter: ref (the reference point a0 on the wanted side of the interval) must be given')
+    ref = float(ref)
+    if a >= b:
+        raise ValueError('cheb_filter: the interval needs a < b, got %r' % ((a, b),))
+    if a <= ref <= b:
+        raise ValueError('cheb_filter: ref = %r lies inside the unwanted interval %r; it must lie strictly outside, on the '
+                         'wanted side' % (ref, (a, b)))
+    return ChebyshevFilter(op, degree, a, b, ref)
+
+
+FILTER_RANGE = 2.0 ** 16   # largest T_d(z0) `cheb_filter_for` allows: see `cheb_filter_degree_cap`
+
+
+def cheb_filter_degree_cap(a, b, a0):
+    """The largest degree d with ``T_d(z0) <= 2**16``, ``z0 = |a0 - c| / e`` (at least 1).  A wanted eigenvalue may lie anywhere
+    between `a0` and the cut, where ``rho`` falls from 1 to ``1 / T_d(z0)``.  Lanczos on ``B = rho(A)`` resolves an
+    eigenvector of B to about ``eps |B|`` absolutely, so the residual on `A` of a pair whose ``rho`` is ``1 / T_d(z0)`` cannot
+    be brought below about ``eps T_d(z0) |A|``: with ``T_d(z0) <= 2**16`` that floor is ``2**-36``, about 1.5e-11, one decade
+    below the eigensolver's default ``reltol``.  (Beyond ``2**26`` such a pair is invisible altogether: the recurrence's
+    breakdown test is ``beta <= 2**-26 tmax``.)  A bound from the arithmetic, not a tuned number; it binds where the wanted
+    end is well separated, which is where a filter has little to offer anyway."""
+    z0 = abs(float(a0) - 0.5 * (float(b) + float(a))) / (0.5 * (float(b) - float(a)))
+    return max(1, int(math.acosh(FILTER_RANGE) / math.acosh(z0)))
+
+
+def cheb_filter_for(op, nev, which='SA', degree=16, steps=None, seed=1):
+    """A :func:`cheb_filter` for the `nev` smallest (``'SA'``) or largest (``'LA'``) eigenvalues of `op`, its interval chosen
+    from a pilot run ``lanczos(op, steps=steps or default_ncv(n, nev), seed=seed)``.  For ``'SA'``, with `ritz` ascending and
+    zero-based: ``a = ritz[nev]``, `b` the Gershgorin upper end, ``a0 = ritz[0] - residuals[0]``; ``'LA'`` is the mirror
+    (``b = ritz[-1 - nev]``, `a` the Gershgorin lower end, ``a0 = ritz[-1] + residuals[-1]``).  By Cauchy interlacing
+    ``ritz[i] >= lambda_i``, so the cut never lies below the (nev+1)-th eigenvalue: the wanted eigenvalues stay outside the
+    damped interval whatever the pilot run found.  That is a guarantee, not a tuned number, and it is loose: a tighter
+    ``interval=`` of :func:`cheb_filter`, from a rough first solve, converges in fewer steps.  ValueError if the pilot run
+    gives fewer than ``nev + 1`` Ritz values or `a0` falls inside the interval.  `degree` is an upper limit: the object's
+    `degree` is ``min(degree, cheb_filter_degree_cap(a, b, a0))``, so that no wanted eigenvalue is damped beyond what the
+    eigensolver's tolerance can recover.  The object records the pilot run's products as `pilotMatvec` (and the run itself as
+    `pilot`)."""
+    from .trlan import default_ncv
+    _device_matrix(op, 'cheb_filter_for', 'the Chebyshev filter')
+    if which not in ('SA', 'LA'):
+        raise ValueError("cheb_filter_for: which must be 'SA' or 'LA', got %r" % (which,))
+    n = int(op.shape[0])
+    nev = _checked_int('cheb_filter_for', 'nev', nev, 1, max(n - 1, 1))
+    degree = _checked_int('cheb_filter_for', 'degree', degree, 1, _lib.MK_FILTER_MAX_DEGREE)
+    pilot = lanczos(op, steps=default_ncv(n, nev) if steps is None else steps, seed=seed)
+    if len(pilot.ritz) < nev + 1:
+        raise ValueError('cheb_filter_for: the pilot run gave %d Ritz values, %d are needed for the cut behind the %d wanted '
+                         'eigenvalues (more steps, or a breakdown: the matrix has few distinct eigenvalues)'
+                         % (len(pilot.ritz), nev + 1, nev))
+    if which == 'SA':
+        interval, ref = (float(pilot.ritz[nev]), None), float(pilot.ritz[0] - pilot.residuals[0])
+    else:
+        interval, ref = (None, float(pilot.ritz[-1 - nev])), float(pilot.ritz[-1] + pilot.residuals[-1])
+    cut = interval[0] if which == 'SA' else interval[1]
+    if (which == 'SA' and not ref < cut) or (which == 'LA' and not ref > cut):
+        raise ValueError('cheb_filter_for: the reference point %r does not lie on the wanted side of the cut %r (the pilot '
+                         "run's extreme Ritz values coincide)" % (ref, cut))
+    try:
+        probe = cheb_filter(op, 1, interval, ref)            # (resolves the Gershgorin end)
+        try:
+            interval = probe.interval
+        finally:
+            probe.free()
+        F = cheb_filter(op, min(degree, cheb_filter_degree_cap(interval[0], interval[1], ref)), interval, ref)
+    except _lib.MkError as err:                              # (a0 inside once the Gershgorin end is known, a < b violated)
+        raise ValueError('cheb_filter_for: %s' % err)
+    F.pilot = pilot
+    F.pilotMatvec = int(pilot.steps)
+    return F
+
+
+class ChebyshevFilter(LinearOperator):
+    """``rho(A)`` of a symmetric device matrix, resident in HBM (`cheb_filter`, `cheb_filter_for`): ``F * v`` on a NumPy
+    vector, `apply_device` on DeviceArray vectors (the input is not modified), ``filter=F`` of :class:`ThickRestartLanczos`.
+    The C ABI has no function for it: the object is a thick-restart Lanczos solver handle created with the block
+    ``mk_params_filter`` in its probe mode (``restart = 1``), whose set-up applies the filter.  Attributes: `degree`,
+    `interval` (``(a, b)`` as used), `ref`, `side` (``'SA'`` / ``'LA'``: the end `ref` lies at), `coefficients` (``c``,
+    ``e`` and the arrays ``p``, ``q`` of the steps), `pilotMatvec` (products of the pilot run that chose the interval; 0 for a
+    given one), `info` (a dict), `free()`.  It is no preconditioner: as ``precon=`` it would be applied through the host
+    like any operator."""
+
+    _info_names = ('rows', 'degree', 'side', 'launches', 'bytes', 'setup_us', 'a_default', 'b_default')
+
+    def __init__(self, op, degree, a, b, ref):
+        from .generic import DeviceRun
+        self._lib = _lib.init()
+        self.degree = int(degree)
+        self.pilot, self.pilotMatvec = None, 0
+        self._op, self._n = op, int(op.shape[0])
+        self._in = self._out = None
+        self._run = DeviceRun(op, _lib.MK_TRLAN, None, abstol=0.0, reltol=0.0, matvec_max=1, restart=1,
+                              eig=(1, 2, 0, 0, 1), filter=(self.degree, a, b, ref))
+        try:
+            self._table = self._run.vector(2)                # (nev + 1: the filter's table)
+        except Exception:
+            self._run.close()
+            raise
+        LinearOperator.__init__(self, self._n, self._n, matvec=self._apply, symmetric=True, dtype=np.float64)
+
+    def _live(self):
+        if self._run is None:
+            raise ValueError('the Chebyshev filter has been freed')
+        return self._run
+
+    interval = property(lambda self: (float(self._table[0]), float(self._table[1])), doc="``(a, b)`` as used.")
+    ref = property(lambda self: float(self._table[2]), doc="The reference point a0.")
+    side = property(lambda self: 'LA' if self._table[2] > self._table[1] else 'SA',
+                    doc="``'SA'`` if `ref` lies below the interval (the smallest eigenvalues are wanted), ``'LA'`` if above.")
+
+    @property
+    def coefficients(self):
+        "``(c, e, p, q)``: the centre and the half width of the interval and the coefficient arrays of the steps 1 .. degree."
+        t = self._table[:5 + 2 * self.degree]
+        return float(t[3]), float(t[4]), t[5::2].copy(), t[6::2].copy()
+
+    @property
+    def info(self):
+        "rows, degree, side (0 / 1), launches per apply, device bytes held, set-up time (us), whether a / b is Gershgorin's."
+        return dict(zip(self._info_names, (int(v) for v in self._table[5 + 2 * self.degree:])))
+
+    def _times_vector(self, x):
+        self._live()                                         # (a freed object says so before anything else)
+        return LinearOperator._times_vector(self, x)
+
+    def _probe(self, ptr):
+        "The solver's set-up applies the filter to the vector at `ptr`; returns the device pointer of the result."
+        run = self._live()
+        _lib.check(self._lib.mk_solver_setup(run.handle, ptr, None))
+        out = ctypes.c_void_p()
+        _lib.check(self._lib.mk_solver_x(run.handle, ctypes.byref(out)))
+        return out.value
+
+    def _apply(self, r):
+        self._live()
+        if self._in is None:
+            self._in = _lib.DeviceArray(self._n, zero=False)
+        self._in.upload(np.ascontiguousarray(r, dtype=np.float64))
+        return _lib.download(self._probe(self._in.ptr), self._n)
+
+    def apply_device(self, d_in, d_out):
+        "``d_out = self * d_in`` on DeviceArray vectors (`d_in is d_out` allowed: the result is formed in the object's own vector)."
+        self._live()
+        for d in (d_in, d_out):
+            if not isinstance(d, _lib.DeviceArray) or d.n != self._n or d.dtype != np.float64 or not d.ptr:
+                raise ValueError('apply_device needs live float64 DeviceArray vectors of %d entries' % self._n)
+        _lib.check(self._lib.mk_memcpy_d2d(d_out.ptr, self._probe(d_in.ptr), 8 * self._n))
+
+    def free(self):
+        if getattr(self, '_in', None) is not None:
+            self._in.free()
+            self._in = None
+        if getattr(self, '_run', None) is not None:
+            self._run.close()
+            self._run = None
+        self._op = None
+
+    def __del__(self):
+        self.free()
 
 
 def _pattern_power(indptr, indices, n, power):
