@@ -230,7 +230,8 @@ MK_API int mk_csr_create_callback(int64_t nrows, int64_t ncols, mk_matvec_fn fn,
  * gather path of format 0.
  * mk_csr_format_info reports what is in use: the format, the number of windowed tiles, the LDS chunks (128
  * doubles each) a workgroup reserves (format 3: the number of column phases), the dictionary size and the bytes of
- * matrix data (everything except x and y) one product streams. */
+ * matrix data (everything except x and y) one product streams (a format 9 matrix with z-uniform pattern bytes,
+ * mk_csr_march_info [12]: three planes of bytes and the pattern table, not one byte per row). */
 MK_API int mk_csr_set_format(mk_csr *A, int fmt);
 MK_API int mk_csr_format_info(const mk_csr *A, int32_t *fmt, int64_t *tiles_windowed, int32_t *lds_chunks,
                        int32_t *dict_size, int64_t *matrix_bytes_per_product);
@@ -274,12 +275,14 @@ MK_API int mk_csr_pencil_info(const mk_csr *A, int64_t *stride_line, int64_t *st
  *   [7] planes per chunk                       [8] chunks                    [9] 2 = general geometry (partly empty bricks, pairs
  *   at any 8-byte boundary: a lane whose row does not exist -- in-line position >= L or in-plane index >= P -- discards its
  *   row sum), 0 = whole aligned bricks          [10] per: bricks per XCD of the XCD-contiguous deal, 0 = round robin
- *   [11] row patterns (format 9).
+ *   [11] row patterns (format 9)               [12] 1 = z-uniform pattern bytes: every interior plane (1 .. planes - 2) carries
+ *   the bytes of plane 1 (checked on the bytes when the format is built, planes >= 3) and the march reads them there -- one
+ *   plane that stays in L2 instead of one byte per row from HBM in every product; the product's bits are the same.
  * Item i of a launch whose grid is a multiple of 8 with per > 0: brick (i % 8) per + (i / 8) % per of chunk (i / 8) / per
  * (8 per item slots per chunk; a slot whose brick number is >= bricks per plane is empty); otherwise brick i % bpp of
  * chunk i / bpp.  Brick j starts at row (j / bx) 4L + (j % bx) 128 of a plane.  A 5-point matrix (one far stride M) is
  * reported as L = 128, P = M: it is marched line by line.  At most `cap` entries are written (MK_MARCH_INFO_LEN exist). */
-#define MK_MARCH_INFO_LEN 12
+#define MK_MARCH_INFO_LEN 13
 MK_API int mk_csr_march_info(const mk_csr *A, int64_t *info, int32_t cap);
 
 /* y = A x   (K1; `self.op * p`, pykrylov/cg/cg.py:115 and every other solver).
@@ -435,6 +438,21 @@ typedef struct {
     uint64_t seed;            /* of the hashed start vector (mk_solver_setup with a NULL start); MK_LOBPCG: column j takes seed + j */
 } mk_params_eig;
 
+/* The long parameter block of MK_CG's ring of directions (the deferred x update, mk_solver_unapplied below): mk_params followed
+ * by a bound on the ring depth m.  Told apart by struct_size = sizeof(mk_params_ring); every solver kind accepts it, only
+ * MK_CG reads the tail.  Without it -- and with MK_CG_XDEFER unset -- a set-up takes m = 1 where a vector is at most 256 MiB
+ * and otherwise the deepest m <= 32 whose buffers beyond the first two fit an eighth of the device memory that is free: at
+ * 512^3 m = 32, 31 GiB beyond the pair.  The bound caps that rule AND an explicit MK_CG_XDEFER (the environment chooses
+ * below the caller's bound, never above it).  A placement search (several solver objects alive at once, each probed with a
+ * few passes, one kept and set up again) creates its objects with {8, 1}: every probe runs at the same depth and holds 7
+ * vectors beyond the pair, and only the kept object's second set-up grows its ring.  The ring grows in mk_solver_setup only
+ * and never shrinks while the solver lives.  MK_ERR_ARG unless 0 <= xdefer_cap <= 32 and xdefer_cap_setups >= 0. */
+typedef struct {
+    mk_params base;
+    int32_t xdefer_cap;         /* upper bound on m, 1 .. 32; 0 = none */
+    int32_t xdefer_cap_setups;  /* the bound holds for the first k set-ups of the solver object; 0 = for every set-up */
+} mk_params_ring;
+
 typedef struct {
     int32_t struct_size;
     int32_t halted;           /* the loop condition of the reference became false */
@@ -449,7 +467,9 @@ typedef struct {
     double residNorm0;
     double threshold;
     double Anorm, Acond, Arnorm, ynorm, xnorm;
-    double aux[8];            /* MK_GMRES: [0] restarts, [1] steps of the last cycle, [2] bytes of the basis */
+    double aux[8];            /* MK_CG: [0] the last <p, A p>, [1] the ring depth m of the deferred x update that the last set-up chose
+                               * (0: three-kernel passes, 1: x rides in the fused product kernel; mk_params_ring) */
+                              /* MK_GMRES: [0] restarts, [1] steps of the last cycle, [2] bytes of the basis */
                               /* MK_IDR: [0] the s in use (after clamping to n), [1] completed cycles, [2] bytes of P, G and U,
                                * [3] breakdown: 0 none, 1 a zero or non-finite pivot M[k,k], 2 a zero or non-finite om */
                               /* MK_PCG: [0] the flexible flag in use, [1] breakdown: 0 none, 1 the curvature test <p, A p> > 0 failed
@@ -1013,8 +1033,8 @@ MK_API int mk_solver_history(const mk_solver *s, double *hist_host, int64_t cap)
  * mk_solver_x / mk_solver_vector always hand out the up-to-date iterate (formed into scratch vectors between passes).
  * Environment MK_CG_FUSE=0 turns it off.  Valid after mk_solver_setup. */
 MK_API int mk_solver_fused(const mk_solver *s, int32_t *fused);
-/* Fused CG passes with a DEFERRED x update (environment MK_CG_XDEFER = m, 1 ... 32; default 8 where a vector is larger than
- * 256 MiB, else 1): x is an accumulator that the loop never reads, so the product kernel leaves it alone (33 bytes per row
+/* Fused CG passes with a DEFERRED x update (environment MK_CG_XDEFER = m, 1 ... 32; default 1 where a vector is at most
+ * 256 MiB, else the deepest m <= 32 that fits an eighth of the free device memory, see mk_params_ring): x is an accumulator that the loop never reads, so the product kernel leaves it alone (33 bytes per row
  * besides the matrix data: p, r in; p, A p out), the directions stay in a ring of m + 1 buffers and one sweep applies m of
  * them to x -- each `x += alpha p` rounded on its own, in order: every bit unchanged.  mk_solver_iterate applies whatever its
  * passes left before it returns, so this count -- completed passes whose direction has not reached x yet -- is 0 after every

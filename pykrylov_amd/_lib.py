@@ -59,6 +59,13 @@ class MkParamsFilter(ctypes.Structure):
     _fields_ = [("eig", MkParamsEig), ("degree", c_i32), ("filter_reserved", c_i32), ("a", c_f64), ("b", c_f64), ("a0", c_f64)]
 
 
+class MkParamsRing(ctypes.Structure):
+    """mk_params_ring (include/mikrylov.h): mk_params followed by a bound on the depth of MK_CG's ring of directions -- at most
+    `xdefer_cap` (0: none) for the first `xdefer_cap_setups` set-ups of the solver object (0: all); mk_solver_create takes
+    `.base`."""
+    _fields_ = [("base", MkParams), ("xdefer_cap", c_i32), ("xdefer_cap_setups", c_i32)]
+
+
 class MkRowOp(ctypes.Structure):
     "mk_rowop (include/mikrylov.h): one step of a composed operator."
     _fields_ = [("code", ctypes.c_int32), ("has_scale", ctypes.c_int32), ("scale", ctypes.c_double),

@@ -29,12 +29,12 @@
 // own: the bits of m sweeps.  x costs 16 n / m + 8 n bytes per pass instead of 16 n.
 #include "mk_solver.h"
 #include "mk_cg_epi.h"
+#include "mk_ringdepth.h"
 
 namespace {
 
 enum { S_RY0 = 0, S_RY1 = 1, S_THRESH = 2, S_RESID = 3, S_RESID0 = 4, S_PAP = 5, S_ALPHA = 6, S_BETA = 7, S_PENDING = 8,
        S_ARING = 32 };                                     // alpha of pass k at S_ARING + k % (m + 1) (deferred x)
-constexpr int MK_XD_MAX = 32;                              // cap of MK_CG_XDEFER
 static_assert(S_ARING + MK_XD_MAX + 1 <= MK_NSCAL, "the alpha ring lives in the scalar file");
 
 // K1: the product epilogue CgSpmvEpiT<NTY> lives in mk_cg_epi.h (PCG, mk_pcg.hip, launches the same product kernels)
@@ -331,6 +331,7 @@ struct CgSolver : mk_solver {
     // nx entries: a slab keeps the neighbours' planes of the direction behind the own rows
     std::vector<double *> ring;
     int xdefer = 1;                                       // m of this solve: x is swept once per m passes (1: inside K1f)
+    int setups_done = 0;                                  // set-ups that chose a depth so far (mk_params_ring: a bound for the first k)
     mutable int64_t x_applied = 0;                        // deferred x: directions [0, x_applied) have been asked to be applied
     mutable double *d_xv = nullptr, *d_pv = nullptr;      // the iterate / direction as a caller sees them between passes
     mutable bool flushed = false;
@@ -351,24 +352,38 @@ struct CgSolver : mk_solver {
     static bool want_fuse() {
         return mk_switch_int<MK_SW_CG_FUSE>() != 0;        // (read at every setup: tests switch it between solves)
     }
-    // MK_CG_XDEFER = m (read at every setup like MK_CG_FUSE).  Unset: 8 where the vectors lie beyond the Infinity Cache -- the
-    // deferral saves HBM traffic and costs one kernel boundary per m passes, so a problem whose x stays in the cache has
-    // nothing to gain from it -- and 1 elsewhere.
+    // MK_CG_XDEFER = m (read at every setup like MK_CG_FUSE).  Unset: the rule of mk_ringdepth.h -- 1 where the vectors stay in the
+    // Infinity Cache (the deferral saves HBM traffic and costs one kernel boundary per m passes, so a problem whose x stays in
+    // the cache has nothing to gain from it), beyond that the deepest ring the memory rule serves.  The caller's
+    // bound (mk_params_ring: a placement search holds several solvers at once and probes them at one depth) caps either.
     int want_xdefer() const {
         static_assert(mk_switch_table[MK_SW_CG_XDEFER].hi == MK_XD_MAX, "the ring holds at most MK_XD_MAX + 1 directions");
         const MkSwitchVal m = mk_switch<MK_SW_CG_XDEFER>();
-        return m.set ? (int)m.v : (sizeof(double) * (size_t)n > ((size_t)256 << 20) ? 8 : 1);
+        const int cap = (ring_cap > 0 && (ring_cap_setups == 0 || setups_done < ring_cap_setups)) ? ring_cap : MK_XD_MAX;
+        if (m.set) return (int)m.v < cap ? (int)m.v : cap;
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
+            (void)hipGetLastError();
+            fr = 0;
+        }
+        return mk_ring_depth(sizeof(double) * (size_t)n, fr, (int)ring.size(), cap);
     }
     // grow the ring towards m + 1 buffers; returns the m it can serve (0: not even the pair of today's fused pass).  The buffers
-    // beyond the pair may take an eighth of the device memory that is free: a placement search holds several solvers at once.
+    // beyond the pair may take an eighth of the device memory that is free (mk_ring_fit): a placement search holds several
+    // solvers at once.  Only ever called from setup(): pbuf() ties the slot of the current direction to m.
     int ring_reserve(int m) {
         const size_t bytes = sizeof(double) * (size_t)nx;
-        while ((int)ring.size() < m + 1) {
-            if (ring.size() >= 2) {
-                const size_t extra = (ring.size() - 2) * bytes;
-                size_t fr = 0, tot = 0;
-                if (hipMemGetInfo(&fr, &tot) != hipSuccess || extra + bytes > (fr + extra) / 8) break;
+        if ((int)ring.size() < m + 1 && m > 1) {
+            size_t fr = 0, tot = 0;
+            if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
+                (void)hipGetLastError();
+                fr = 0;
             }
+            const int fit = mk_ring_fit(bytes, fr, (int)ring.size());
+            const int have = (int)ring.size() - 1;
+            m = m < fit ? m : (fit > have ? fit : have);     // (what the ring holds already is never given up)
+        }
+        while ((int)ring.size() < m + 1) {
             double *v = nullptr;
             if (alloc_vec(&v, nx) != MK_OK) {
                 (void)hipGetLastError();                     // (reported by the fall-back, not by the next launch check)
@@ -464,6 +479,7 @@ struct CgSolver : mk_solver {
                 fused = false;
             }
         }
+        setups_done += 1;
         if (mk_comm_active()) {
             // The choice changes what travels: fused ranks exchange r's boundary planes and form the neighbours' p themselves,
             // the others exchange p -- messages of the same size, so a disagreement would neither hang nor fail, it would
@@ -585,6 +601,7 @@ struct CgSolver : mk_solver {
         res->threshold = h_scal[S_THRESH];
         res->converged = (h_scal[S_RESID] <= h_scal[S_THRESH]) ? 1 : 0;     // cg.py:161
         res->aux[0] = h_scal[S_PAP];
+        res->aux[1] = fused ? (double)xdefer : 0.0;          // the ring depth m this set-up chose (0: three-kernel passes)
         return MK_OK;
     }
 

@@ -85,6 +85,7 @@ struct MkCsrView {
     // pen_xtop = the input vector's last entry (pair loads are clamped to it); pen_dump = where discarded rows are stored
     int pen_gen, pen_per;
     int pen_nol;                                            // the matrix has no +-L entries at all (a 5-point matrix: L is a fiction)
+    int pen_zuni;                                           // the interior planes' pattern bytes are plane 1's: read there (256 KiB at 512^3, L2 hits)
     int64_t pen_xtop;
     double *pen_dump;
     // resident tiles (fmt 3): LDS capacity per tile in nonzeros (multiple of 256), column phases and their width
@@ -260,6 +261,7 @@ static inline MkCsrView mk_view(const mk_csr *A) {
         v.pen_gen = P->pen_gen;
         v.pen_per = P->pen_per;
         v.pen_nol = P->pen_nol;
+        v.pen_zuni = P->pen_zuni;                            // (a slab's plan checked the slab's own bytes; mk_view_part keeps it)
         v.pen_xtop = A->x_len() - 1;
         v.pen_dump = P->pen_gen ? mk_pen_dump() : nullptr;
     } else if (v.fmt == MK_ST_RESIDENT) {

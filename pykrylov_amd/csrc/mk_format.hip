@@ -1177,6 +1177,19 @@ __global__ __launch_bounds__(MK_BLOCK) void pen_sym_pack(int64_t nrows, int64_t 
         sym[i] = i < 4 * nrows ? sval[3 * nrows + i] : sval[i - 4 * nrows];
 }
 
+// z-uniform pattern bytes (formats 9 - 11): does every interior plane carry the bytes of plane 1 -- pid[z P + i] == pid[P + i] for
+// 1 <= z <= nz - 2 and every i?  Then the march reads the interior planes' bytes from plane 1 (mk_spmv_fmt9.h).  A test on the
+// bytes, not on geometry: a slab's first and last planes are data like any other.  state[1] is raised by the first difference;
+// launched for nz >= 4 (planes 2 .. nz - 2 are compared).
+__global__ __launch_bounds__(MK_BLOCK) void pen_zuniform(int64_t P, int64_t nz, const uint8_t *__restrict__ pid, int *state) {
+    const int64_t cnt = (nz - 3) * P;
+    for (int64_t i = (int64_t)blockIdx.x * MK_BLOCK + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * MK_BLOCK)
+        if (pid[2 * P + i] != pid[P + i % P]) {
+            state[1] = 1;
+            return;
+        }
+}
+
 // Below this many rows the windowed pattern format (fmt 4) keeps the matrix: a brick march needs a few thousand
 // (brick, chunk) items of >= 8 planes to fill the chip, and a cache-resident product is latency bound either way
 int64_t pencil_min_rows() { return mk_switch_int<MK_SW_PENCIL_MIN_ROWS>(); }
@@ -1284,6 +1297,13 @@ bool pencil_plan(const mk_csr *A, MkPlan &P, bool forced, int want) {
         return hipMemcpyAsync(h_state, d_state, sizeof(h_state), hipMemcpyDeviceToHost, st) == hipSuccess &&
                hipStreamSynchronize(st) == hipSuccess;
     };
+    auto zuniform = [&](const uint8_t *bytes) -> int {      // (after the kernel that wrote them, while d_state lives)
+        const int64_t nzl = A->nrows / PP;
+        if (nzl < 4) return nzl == 3 ? 1 : 0;                // (three planes: plane 1 is the whole interior)
+        if (hipMemsetAsync(d_state, 0, 2 * sizeof(int), st) != hipSuccess) return 0;
+        hipLaunchKernelGGL(pen_zuniform, dim3(grid), dim3(MK_BLOCK), 0, st, PP, nzl, bytes, d_state);
+        return (read_state() && hipGetLastError() == hipSuccess && !h_state[1]) ? 1 : 0;
+    };
     if (!reset_set()) return drop();
     int gnz = (int)((A->nnz + MK_BLOCK - 1) / MK_BLOCK);
     hipLaunchKernelGGL(dict_collect, dim3(gnz > 512 ? 512 : gnz), dim3(MK_BLOCK), 0, st, A->nnz, A->d_data, d_table, d_state);
@@ -1325,6 +1345,7 @@ bool pencil_plan(const mk_csr *A, MkPlan &P, bool forced, int want) {
                 }
             }
         }
+        P.pen_zuni = zuniform(d_pid);
         hipFree(d_stats);
         hipFree(d_table);
         hipFree(d_dict);
@@ -1357,6 +1378,7 @@ bool pencil_plan(const mk_csr *A, MkPlan &P, bool forced, int want) {
                        L, PP, sl, d_table, d_state, (const double *)d_keys, nkeys, d_pid);
     hipLaunchKernelGGL(pen_table, dim3(1), dim3(MK_BLOCK), 0, st, nkeys, d_keys, d_dict, d_tab);
     if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return drop();
+    P.pen_zuni = zuniform(d_pid);
     hipFree(d_stats);
     hipFree(d_table);
     hipFree(d_keys);
@@ -1536,8 +1558,11 @@ extern "C" int mk_csr_format_info(const mk_csr *A, int32_t *fmt, int64_t *tiles_
         if (tiles_windowed) *tiles_windowed = 0;
         if (lds_chunks) *lds_chunks = 0;
         if (dict_size) *dict_size = P->ndict;
+        // (physical: a z-uniform format 9 matrix reads the bytes of three planes -- the first, plane 1 for the whole interior, the
+        //  last.  Formats 10 / 11 keep reporting the byte per row beside their 56 / 32: 3 % of what they stream)
+        const int64_t bytes = (P->fmt == MK_ST_MARCH && P->pen_zuni) ? 3 * P->pen_P : A->nrows;
         if (matrix_bytes_per_product)
-            *matrix_bytes_per_product = A->nrows + (P->fmt == MK_ST_MARCH ? 64 * (int64_t)P->npat : (P->fmt == MK_ST_MARCH_STREAM ? 56 : 32) * A->nrows);
+            *matrix_bytes_per_product = bytes + (P->fmt == MK_ST_MARCH ? 64 * (int64_t)P->npat : (P->fmt == MK_ST_MARCH_STREAM ? 56 : 32) * A->nrows);
         return MK_OK;
     }
     const bool windowed = mk_fmt_windowed(P->fmt);
@@ -1627,7 +1652,7 @@ extern "C" int mk_csr_march_info(const mk_csr *A, int64_t *info, int32_t cap) {
     const bool on = mk_fmt_march(P->fmt);
     const int64_t v[MK_MARCH_INFO_LEN] = {on ? P->fmt : 0, P->pen_L, P->pen_P, P->pen_nz, P->pen_ny, P->pen_bx,
                                           P->pen_bx ? P->pen_bpp / P->pen_bx : 0, P->pen_zc, P->pen_chunks, P->pen_gen, P->pen_per,
-                                          P->npat};
+                                          P->npat, P->pen_zuni};
     for (int k = 0; k < cap && k < MK_MARCH_INFO_LEN; ++k) info[k] = on ? v[k] : 0;
     return MK_OK;
 }

@@ -160,7 +160,8 @@ struct mk_solver {
     double sigma[MK_MSCG_MAX_SHIFTS] = {};
     int eig_nev = 0, eig_ncv = 0, eig_which = 0, eig_keep = 0;   // MK_TRLAN, MK_LOBPCG, MK_TRSVD: the tail of their long parameter block (mk_params_eig)
     uint64_t eig_seed = 0;
-    int64_t n = 0;        // local rows = length of every solver vector
+    int ring_cap = 0, ring_cap_setups = 0;       // MK_CG: the tail of mk_params_ring (0: no bound on the ring depth; 0: at every set-up)
+    int64_t n = 0;       // local rows = length of every solver vector
     int64_t nx = 0;       // length of vectors that feed an SpMV (n + halo)
     hipStream_t stream = nullptr;
 

@@ -299,12 +299,17 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
     const mk_params_shifts *shifts = nullptr;
     const mk_params_eig *eig = nullptr;
     const mk_params_filter *filt = nullptr;                  // ... or, behind the eigenproblem, the Chebyshev filter of MK_TRLAN
+    const mk_params_ring *ringp = nullptr;                   // ... or a bound on the depth of MK_CG's ring of directions
     if (params->struct_size == (int32_t)sizeof(mk_params_filter)) {
         filt = reinterpret_cast<const mk_params_filter *>(params);
         eig = &filt->eig;
     } else if (params->struct_size == (int32_t)sizeof(mk_params_shifts)) shifts = reinterpret_cast<const mk_params_shifts *>(params);
     else if (params->struct_size == (int32_t)sizeof(mk_params_eig)) eig = reinterpret_cast<const mk_params_eig *>(params);
+    else if (params->struct_size == (int32_t)sizeof(mk_params_ring)) ringp = reinterpret_cast<const mk_params_ring *>(params);
     else MK_ARG(params->struct_size == (int32_t)sizeof(mk_params));
+    if (ringp && (ringp->xdefer_cap < 0 || ringp->xdefer_cap > 32 || ringp->xdefer_cap_setups < 0))
+        return mk_fail(MK_ERR_ARG, "mk_solver_create: xdefer_cap = %d, must be 0 (no bound) .. 32, for xdefer_cap_setups = %d >= 0 "
+                       "set-ups (0: all)", (int)ringp->xdefer_cap, (int)ringp->xdefer_cap_setups);
     mk_solver *s = nullptr;
     switch (params->kind) {
         case MK_CG: s = mk_make_cg(); break;
@@ -451,6 +456,10 @@ extern "C" int mk_solver_create(const mk_csr *A, const mk_params *params, mk_sol
     if (shifts && params->kind == MK_MSCG) {
         s->nsigma = shifts->nsigma;
         memcpy(s->sigma, shifts->sigma, sizeof(double) * (size_t)shifts->nsigma);
+    }
+    if (ringp && params->kind == MK_CG) {
+        s->ring_cap = ringp->xdefer_cap;
+        s->ring_cap_setups = ringp->xdefer_cap_setups;
     }
     int rc = s->init_common(A, params);
     if (rc != MK_OK) {

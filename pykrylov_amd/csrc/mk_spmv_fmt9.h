@@ -156,6 +156,7 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
     const int64_t off_lo = A.pen_xlo >= 0 ? A.pen_xlo : (int64_t)0;
     const int64_t off_hi = A.pen_xhi >= 0 ? A.pen_xhi : (int64_t)(nz - 1) * P;
     const uint8_t *pid = A.pid;
+    const bool zuni = A.pen_zuni != 0;
     // the pattern table, 16 words per pattern, behind the plane images (read-only after this copy)
     [[maybe_unused]] unsigned *ptl = reinterpret_cast<unsigned *>(smem + MK_PEN_LDS);
     if constexpr (!STREAM) {
@@ -244,8 +245,12 @@ __device__ __forceinline__ void mk_spmv_tiles_fmt9(const MkCsrView &A, const dou
                 hr[d] = epi.fuse_r[clampr((int64_t)p * P + hc)];
                 er[d] = epi.fuse_r[clampr((int64_t)p * P + ec)];
             }
-            if constexpr (GEN) pidr[d] = *reinterpret_cast<const mk_u16u *>(pid + (int64_t)p * P + c);   // (the array has slack behind it)
-            else pidr[d] = *reinterpret_cast<const uint16_t *>(pid + (int64_t)p * P + c);
+            // z-uniform bytes (MkPlan::pen_zuni): every interior plane carries plane 1's, so they are read THERE -- one plane of
+            // bytes that stays in L2 instead of n of them from HBM per product; the same bytes, so the same bits.  Workgroup
+            // uniform: a scalar select of the plane, the load stays unconditional and the body one basic block.
+            const int pz = (zuni && p > 0 && p < nz - 1) ? 1 : p;
+            if constexpr (GEN) pidr[d] = *reinterpret_cast<const mk_u16u *>(pid + (int64_t)pz * P + c);   // (the array has slack behind it)
+            else pidr[d] = *reinterpret_cast<const uint16_t *>(pid + (int64_t)pz * P + c);
             if constexpr (SYM) {
                 hvr[d] = sv5[clampr((int64_t)p * P + hc)];
                 evr[d] = sv4[clampr((int64_t)p * P + ec)];

@@ -21,7 +21,7 @@ struct MkSwitchRow {
 };
 constexpr MkSwitchRow mk_switch_table[MK_SW_COUNT] = {
     {"MK_CG_FUSE", 'i', 1, INT_MIN, INT_MAX, false, "0: CG keeps its three-kernel pass on brick-march matrices"},
-    {"MK_CG_XDEFER", 'i', 0, 1, 32, false, "fused CG sweeps x once per m passes (auto: 8 where a vector exceeds 256 MiB, else 1)"},
+    {"MK_CG_XDEFER", 'i', 0, 1, 32, false, "fused CG sweeps x once per m passes (auto: 1 up to 256 MiB per vector, beyond it the deepest m <= 32 whose ring fits an eighth of the free memory)"},
     {"MK_ILU_FUSE_ROWS", 'i', 256, 0, INT_MAX, false, "ILU / IC levels of at most this many rows share a launch (0: one launch per level)"},
     {"MK_SPMV_FORMAT", 'i', 11, 0, 11, true, "highest storage format the builder may choose"},
     {"MK_SPMV_NT", 'i', 0, INT_MIN, INT_MAX, true, "non-temporal value loads and product stores (auto: on where a vector exceeds 256 MiB)"},

@@ -256,6 +256,8 @@ class DeviceRun(object):
         # (mk_params_filter) behind `eig`; an end of [a, b] that is None or NaN is the Gershgorin end.  With `restart=1` the
         # run is the filter's probe: set-up applies the filter to `rhs`, `x()` is the result.
         self.filter = params.pop('filter', None)
+        # `ring_cap`: (cap, set-ups) of CG's ring of directions, the tail of the fourth long block (mk_params_ring).
+        ring_cap = params.pop('ring_cap', None)
         self._d_shadow = None
         if draws is not None:
             self.placement_draws = int(draws)
@@ -291,6 +293,11 @@ class DeviceRun(object):
             block.nev, block.ncv, block.which, block.keep, block.seed = [int(v) for v in eig]
             p = block.base                                   # (a view: it writes into the block and keeps it alive)
             p.struct_size = ctypes.sizeof(_lib.MkParamsEig)
+        elif ring_cap is not None:
+            block = self._block = _lib.MkParamsRing()
+            block.xdefer_cap, block.xdefer_cap_setups = [int(v) for v in ring_cap]
+            p = block.base                                   # (a view: it writes into the block and keeps it alive)
+            p.struct_size = ctypes.sizeof(_lib.MkParamsRing)
         elif shifts is None:
             p = _lib.MkParams()
             p.struct_size = ctypes.sizeof(_lib.MkParams)
@@ -447,8 +454,35 @@ class DeviceRun(object):
         self._check(self.lib.mk_sync())
         return (time.perf_counter() - t0) / max(1, done.value) if done.value == passes else float('inf')
 
+    PROBE_RING = (8, 1)                                      # mk_params_ring of a placement probe: m <= 8 at its first set-up
+
+    def _probe_params(self):
+        """The parameter block the objects of a placement search are created with.  CG's ring of directions takes what the
+        memory rule of the library gives it (33 vectors at 512^3), and several objects are alive during the search: each
+        would get a different depth and be timed at it.  So every probe's first set-up is bounded at one depth, and only the
+        kept object's set-up afterwards -- the others are gone by then -- grows the ring.  A caller's own `ring_cap` stays."""
+        p = self._params
+        if p.kind != _lib.MK_CG or p.struct_size != ctypes.sizeof(_lib.MkParams):
+            return p
+        block = self._probe_block = _lib.MkParamsRing()
+        ctypes.memmove(ctypes.byref(block), ctypes.byref(p), ctypes.sizeof(_lib.MkParams))
+        block.base.struct_size = ctypes.sizeof(_lib.MkParamsRing)
+        block.xdefer_cap, block.xdefer_cap_setups = self.PROBE_RING
+        return block.base
+
     def _draw_placement(self, draws):
         self._drawn = True
+        params = self._probe_params()
+        if params is not self._params:                       # (the constructor's object has not been set up: it holds no vectors)
+            h = ctypes.c_void_p()
+            _lib.check(self.lib.mk_solver_create(self.op.handle, ctypes.byref(params), ctypes.byref(h)))
+            try:
+                self._apply_precon(h)
+            except Exception:
+                self.lib.mk_solver_destroy(h)
+                raise
+            self.lib.mk_solver_destroy(self.handle)
+            self.handle = h
         spacers, best, best_t = [], self.handle, None
         t_probe = time.perf_counter()
         per_draw, chosen = [], 0
@@ -462,7 +496,7 @@ class DeviceRun(object):
                     sp_mb = int(os.environ.get('MK_PLACEMENT_SPACER_MB', '176'))
                     spacers.append(_lib.DeviceArray(((sp_mb + (sp_mb // 2) * k) << 20) // 8 + 512 * k, zero=False))
                     h = ctypes.c_void_p()
-                    _lib.check(self.lib.mk_solver_create(self.op.handle, ctypes.byref(self._params), ctypes.byref(h)))
+                    _lib.check(self.lib.mk_solver_create(self.op.handle, ctypes.byref(params), ctypes.byref(h)))
                 except Exception:
                     break                                     # (no memory for another draw: keep what we have)
                 try:

@@ -21,7 +21,7 @@ wl = sys.argv[1] if len(sys.argv) > 1 else "const"
 side = int(sys.argv[2]) if len(sys.argv) > 2 else 512
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 passes = int(sys.argv[4]) if len(sys.argv) > 4 else 96          # a multiple of every m below: whole rings inside a timing
-ms_list = [int(v) for v in os.environ.get("AB_MS", "1,2,4,8,16").split(",")]
+ms_list = [int(v) for v in os.environ.get("AB_MS", "1,2,4,8,16,32").split(",")]
 
 op = gallery.poisson3d(side) if wl == "const" else gallery.poisson3d_varcoef(side)
 n = op.shape[0]
@@ -30,14 +30,16 @@ rhs = _lib.DeviceArray(n)
 op.spmv_device(ones.ptr, rhs.ptr)
 matrix_bytes = n * (1 if wl == "const" else 33)
 
-runs = {}
-for m in ms_list:
+# the deepest ring first: every ring takes at most an eighth of the memory that is free at ITS set-up (csrc/mk_ringdepth.h), and
+# 31 GiB beyond the pair (m = 32 at 512^3) is an eighth of nearly the whole device; `got`: the depth each object was given
+runs, got = {}, {}
+for m in sorted(ms_list, reverse=True):
     os.environ["MK_CG_XDEFER"] = str(m)
     os.environ["MK_PLACEMENT_DRAWS"] = "1"                       # (one object per m: the A/B is between them)
     run = DeviceRun(op, _lib.MK_CG, rhs, None, abstol=0.0, reltol=0.0, matvec_max=1 << 60, check_curvature=1)
     run.setup()
     run.iterate(16)
-    runs[m] = run
+    runs[m], got[m] = run, int(run.finish().aux[1])
 
 t = {m: [] for m in ms_list}
 for r in range(rounds):
@@ -51,8 +53,11 @@ for r in range(rounds):
 
 print("workload %s %d^3, n = %d, %d rounds of %d passes; medians (min .. max)" % (wl, side, n, rounds, passes))
 print("%3s  %21s  %8s  %10s  %9s  %s" % ("m", "ms per pass", "it/s", "GB / pass", "of 8 TB/s", "ring memory"))
-for m in ms_list:
-    a = np.array(t[m])
+for want in ms_list:
+    a = np.array(t[want])
+    m = got[want]
+    if m != want:
+        print("(m = %d asked for, %d served: no memory for a deeper ring)" % (want, m))
     byts = matrix_bytes + (32 + 24) * n + (16 * n if m == 1 else 8 * n + 16 * n / m)
     med = float(np.median(a))
     print("%3d  %6.3f (%6.3f .. %6.3f)  %8.1f  %10.3f  %9.3f  %.2f GB" % (m, med, a.min(), a.max(), 1e3 / med, byts / 1e9,
