@@ -147,11 +147,17 @@ APPLY = (("poisson2d_20", dict(coarse_max=16)),                # the dense inver
          ("1138bus", dict(coarse_max=20)))
 
 
-@pytest.mark.parametrize("fmt", [0, 1, -1], ids=["format0", "format1", "default_format"])
+FORCED = (0, 1, 2, 3, 4)
+IN_USE = {}                                                    # requested storage -> storages the level matrices ended in
+
+
+@pytest.mark.parametrize("fmt", FORCED + (-1,), ids=["format%d" % f for f in FORCED] + ["default_format"])
 @pytest.mark.parametrize("name,kw", APPLY, ids=["inverse", "smoother", "degree3", "1138bus"])
 def test_apply_bits(name, kw, fmt):
     """`M * x`, mk_amg_apply out of place (the input unchanged), with in == out and through `apply_device` equal the restated
-    cycle byte for byte, with A and every P and R forced into storage formats 0 and 1 and in the formats the builder chooses."""
+    cycle byte for byte, with A and every P and R forced into storage formats 0 .. 4 (a request a matrix cannot take degrades;
+    which storage every level matrix ended in is recorded for test_apply_bits_ran_in_the_forced_storages) and in the formats
+    the builder chooses."""
     from pykrylov_amd import _lib, tools
     lib = _lib.init()
     A, H, x, z = reference(name, **kw)
@@ -176,6 +182,12 @@ def test_apply_bits(name, kw, fmt):
     M.apply_device(d_out, d_out)
     assert same(d_out.to_numpy(), H * z), (name, kw, fmt)
     got = ctypes.c_int32()
+    for l in range(M.info["levels"]):                          # (after the applies: what the residual and correction ran in)
+        for h in M.level_handles(l):
+            if h is not None:
+                _lib.check(lib.mk_csr_format_info(h, ctypes.byref(got), None, None, None, None))
+                IN_USE.setdefault(fmt, set()).add(got.value)
+    print("%s %s: request %d, storages of the level matrices %s" % (name, kw, fmt, sorted(IN_USE[fmt])))
     _lib.check(lib.mk_csr_format_info(op.handle, ctypes.byref(got), None, None, None, None))
     print("%s %s: format of A in use %d" % (name, kw, got.value))
     if fmt == 0:
@@ -184,6 +196,13 @@ def test_apply_bits(name, kw, fmt):
     d_out.free()
     M.free()
     op.free()
+
+
+def test_apply_bits_ran_in_the_forced_storages():
+    """MkAmgEpi (residual and correction of the V-cycle) met every storage 0 .. 4: each was in use by at least one level
+    matrix of the case that asked for it."""
+    for fmt in FORCED:
+        assert fmt in IN_USE.get(fmt, ()), (fmt, IN_USE)
 
 
 # ------------------------------------------------------------------ routes
