@@ -115,6 +115,29 @@ def levels(indptr, indices, forward=True):
     return out
 
 
+RUN_MAX = 2048       # levels of one fused run (MK_ILU_RUN_MAX, csrc/mk_ilu.hip)
+BLOCK = 256          # rows per workgroup
+
+
+def plan(level_widths, fuse, run_max=RUN_MAX):
+    """The launches of one sweep as mk_ilu_plan lays them out: a list of (first level, one past the last level, workgroups).
+    A level of more than `fuse` rows is a launch of its own over ceil(rows / 256) workgroups; consecutive levels of at most
+    `fuse` rows each are one launch of ONE workgroup, cut after `run_max` levels; `fuse` = 0: one launch per level."""
+    out = []
+    L, n = 0, len(level_widths)
+    while L < n:
+        if fuse > 0 and level_widths[L] <= fuse:
+            e = L + 1
+            while e < n and e - L < run_max and level_widths[e] <= fuse:
+                e += 1
+            out.append((L, e, 1))
+            L = e
+        else:
+            out.append((L, L + 1, max(1, -(-int(level_widths[L]) // BLOCK))))
+            L += 1
+    return out
+
+
 def apply(indptr, indices, vals, r, kind='ilu0', lev=None):
     """y = M^-1 r level by level (vectorised over a level's rows); the order of every row's subtractions is the column
     order, as on the device.  `lev` = (levels(forward), levels(backward)) to reuse an analysis."""
